@@ -7,6 +7,12 @@ hyperprior -> likelihood/bit count -> synthesis), inputs resident in HBM, seeded
 architecture (pretrained weights and UVG are not available offline).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--model ...] [--precision ...]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `ms_per_step`, `quality`, ...).
+--full adds everything else the line can carry: the `strong` block of the default LHBDC 1080p line, and at N = 1 the roofline /
+kernel-table block, the native-fp32 comparison, the whole-GOP and bitstream rates, the CPU baseline and the parity against the
+CPU oracle.  --dump-outputs DIR writes what the last timed step computed as .npy files (see :func:`dump_outputs`).
 
 N > 1: one rank per GPU.  Started by `python -m torch.distributed.run` the ranks read RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_*; started plainly (`python bench.py --gpus 8`) this process launches that command itself as a CHILD -- before
@@ -246,6 +252,36 @@ class StrongWorkload:
         self.coder = None
 
 
+DUMP_SAMPLES = 1 << 22            # decoded-frame elements written by --dump-outputs (16 MB of float32)
+
+
+def dump_outputs(out_dir, rows, decoded, seed=20240601):
+    """--dump-outputs: what the last timed step computed, as .npy files in ``out_dir`` (the inputs are seeded: two builds given the
+    same arguments can be compared file by file).
+      rd_records.npy             float64 [frames, 6|7]: the gathered per-frame R-D records of the step in (video, frame) order --
+                                 video, frame, hierarchy level, PSNR (dB), bits, pixels (strong scaling: + is_intra)
+      b_frames_sample.npy        float32 [B-frames, S]: the decoded B-frames of this rank (GOP by GOP, in frame order), S elements of
+                                 each at the same fixed, seeded flat positions of the padded NCHW frame
+      b_frames_channel_mean.npy  float64 [B-frames, 3]: per-channel mean of each whole decoded B-frame
+    (strong scaling hands back records only: no frame files)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rd_records.npy"), np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.float64))
+    if decoded is None:
+        return
+    gops = [decoded] if isinstance(decoded, dict) else list(decoded)
+    # boundary frames (first / last key of a GOP) are the decoded I-frames the step was given, not what it computed
+    b_frames = [g[k] for g in gops for k in sorted(g)[1:-1]]
+    numel = b_frames[0].numel()
+    per = min(numel, max(1, DUMP_SAMPLES // len(b_frames)))
+    idx = np.sort(np.random.default_rng(seed).choice(numel, size=per, replace=False) if per < numel else np.arange(numel))
+    idx = torch.from_numpy(idx).to(b_frames[0].device)
+    with torch.no_grad():
+        sample = torch.stack([f.reshape(-1).index_select(0, idx) for f in b_frames]).float().cpu().numpy()
+        means = torch.stack([f.double().mean(dim=(0, 2, 3)) for f in b_frames]).cpu().numpy()
+    np.save(os.path.join(out_dir, "b_frames_sample.npy"), sample.astype(np.float32))
+    np.save(os.path.join(out_dir, "b_frames_channel_mean.npy"), means.astype(np.float64))
+
+
 def physical_cores():
     try:
         import psutil
@@ -317,10 +353,10 @@ def parse_args():
     ap.add_argument("--parity-both-checkpoints", action="store_true",
                     help="repeat the parity block on the other checkpoint kind (one more oracle pass)")
     ap.add_argument("--skip-extras", action="store_true",
-                    help="N = 1: skip the whole-GOP-with-I-frame and real-bitstream blocks (profiling runs: the trace then holds the timed "
+                    help="--full, N = 1: skip the whole-GOP-with-I-frame and real-bitstream blocks (profiling runs: the trace then holds the timed "
                          "region and the one instrumented frame of the roofline block only)")
     ap.add_argument("--no-strong-block", action="store_true",
-                    help="default (weak) LHBDC 1080p line: skip the extra `strong` block (one pass over a configs[3] test set sized by "
+                    help="--full (weak) LHBDC 1080p line: skip the extra `strong` block (one pass over a configs[3] test set sized by "
                          "--strong-seconds, GOP-sharded over the ranks, R-D table checksum)")
     ap.add_argument("--strong-seconds", type=float, default=10.0,
                     help="size of the `strong` block's test set: about this many seconds per pass at the given number of GPUs")
@@ -336,7 +372,14 @@ def parse_args():
                          "(decode workers -> pinned ring -> async H2D) instead of coding device-resident tensors; the synthetic clip "
                          "is written to DIR/<rank>/seq00/*.png first when it is not there yet")
     ap.add_argument("--data-workers", type=int, default=8)
-    ap.add_argument("--kernel-table", default=None, help="write the per-kernel event timing table here (json)")
+    ap.add_argument("--kernel-table", default=None, help="--full: write the per-kernel event timing table here (json)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement and check of the line: the `strong` block (default LHBDC "
+                         "1080p line) and, at N = 1, roofline, native-fp32, whole-GOP, bitstream, CPU baseline and parity blocks; "
+                         "a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (rank 0): the gathered per-frame "
+                         "R-D records and a fixed, seeded sample of the decoded B-frames")
     return ap.parse_args()
 
 
@@ -435,6 +478,7 @@ def main():
         else:
             runners = [None if args.no_graph else vgop.GopGraph(model, H, W, gops=G)]
         counter = [0]
+        last_out = [None]               # what the latest step handed back: the decoded frames (--dump-outputs)
         reader = None
         if args.data:
             if is_flex or is_icip:
@@ -464,16 +508,17 @@ def main():
                     frames[j] = reader.load_frame(*k, out=static[j])
                 reader.prefetch(keys)                       # the next step's frames decode while this step's GOPs are coded
             if runners[i] is not None:
-                runners[i].code(frames, gop_index=rank * G, records=recs)
+                last_out[0] = runners[i].code(frames, gop_index=rank * G, records=recs)
             elif is_icip:
-                vgop.code_gop_icip2024(model, frames, frames[0], frames[16], H, W, i, recs, video=0, gop_index=rank)
+                last_out[0] = vgop.code_gop_icip2024(model, frames, frames[0], frames[16], H, W, i, recs, video=0, gop_index=rank)[0]
             elif is_flex:
                 gops = [frames[17 * g:17 * g + 17] for g in range(G)]
-                vgop.code_gops_flex(model, gops, [(gp[0], gp[16]) for gp in gops], H, W, rate_points[i], recs, video=0,
-                                    first_gop_index=rank * G)
+                last_out[0] = vgop.code_gops_flex(model, gops, [(gp[0], gp[16]) for gp in gops], H, W, rate_points[i], recs, video=0,
+                                                  first_gop_index=rank * G)
             else:
                 gops = [frames[9 * g:9 * g + 9] for g in range(G)]
-                vgop.code_gops_lhbdc(model, gops, [(gp[0], gp[8]) for gp in gops], H, W, recs, video=0, first_gop_index=rank * G)
+                last_out[0] = vgop.code_gops_lhbdc(model, gops, [(gp[0], gp[8]) for gp in gops], H, W, recs, video=0,
+                                                   first_gop_index=rank * G)
         n_warm = max(args.warmup, len(runners))          # every graph is captured before the clock starts
 
     with torch.no_grad():
@@ -491,6 +536,8 @@ def main():
         t_gathered = time.perf_counter() - t0
         barrier()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rows, None if strong else last_out[0])
     if os.environ.get("VC_BENCH_DUMP_RECORDS") and rank == 0:      # debugging aid: the gathered per-frame records, exact (float.hex)
         with open(os.environ["VC_BENCH_DUMP_RECORDS"], "w") as f:
             json.dump([[float(v).hex() for v in r] for r in sorted(rows.tolist())], f)
@@ -580,7 +627,7 @@ def main():
                                    "slowest rank); elapsed_s = up to the closing barrier; value uses the MAX elapsed over ranks"}
     quality_note = ("calibrated seeded weights (trained-like statistics, vcamd.seeding): R-D values are parity references, not the "
                     "published curve" if checkpoint == "calibrated" else "seeded random weights: R-D values are parity references, not codec quality")
-    if (not strong and not is_flex and not is_icip and args.resolution == "1080p" and not f16 and not args.no_strong_block
+    if (args.full and not strong and not is_flex and not is_icip and args.resolution == "1080p" and not f16 and not args.no_strong_block
             and not args.data):
         # ---- the SAME line also carries BASELINE configs[3] (the metric's "1/2/4/8 MI355X" half as a fixed-work measurement):
         # ONE pass over a UVG-shaped test set sized to ~--strong-seconds at this number of GPUs, contiguous GOP ranges per
@@ -662,7 +709,7 @@ def main():
         q = vgop.summarize(rows)
         result["quality"] = {"b_frames": q["frames"], "bpp_estimated": q["bpp"], "psnr_db": q["psnr"], "note": quality_note}
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if strong:
             frames = synthetic_gop(1234, 0, dev, 9, (H, W))
         single_gpu_extras(args, result, model, frames, sd, dev, H, W)
@@ -673,7 +720,7 @@ def main():
 
 
 def single_gpu_extras(args, result, model, frames, sd, dev, H, W):
-    """N = 1 only: roofline of the dominant kernel (HIP events on the launch stream), whole-GOP rate with the I-frame,
+    """--full, N = 1 only: roofline of the dominant kernel (HIP events on the launch stream), whole-GOP rate with the I-frame,
     the CPU baseline (oracle timed on this host) and the parity of the same frame against it."""
     from vcamd import gop as vgop
     from vcamd import hip

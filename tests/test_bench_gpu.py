@@ -47,12 +47,12 @@ def test_self_launched_two_rank_strong_run_equals_single_rank():
 
 
 def test_default_line_carries_the_strong_block_and_its_checksum_is_the_single_rank_one():
-    """The DEFAULT (weak) line of `bench.py --gpus N` also holds BASELINE configs[3] as a `strong` block: one pass over a test
+    """The full (weak) line of `bench.py --gpus N --full` also holds BASELINE configs[3] as a `strong` block: one pass over a test
     set sized by --strong-seconds at N GPUs, GOP-sharded, R-D records gathered, per-rank coding times, and a checksum over the
     records of the frames every world size codes -- which must equal the single-rank run's, bit pattern for bit pattern."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    args = ["--sequences", "2", "--strong-seconds", "1", "--steps", "1", "--warmup", "0", "--gops-per-step", "1", "--no-cpu-baseline"]
+    args = ["--full", "--sequences", "2", "--strong-seconds", "1", "--steps", "1", "--warmup", "0", "--gops-per-step", "1", "--no-cpu-baseline"]
 
     def run(extra, env_extra=None):
         env = dict(os.environ)
@@ -105,3 +105,33 @@ def test_bench_streams_frames_from_png_files(tmp_path):
     assert streamed["quality"]["b_frames"] == resident["quality"]["b_frames"] == 7
     assert streamed["quality"]["bpp_estimated"] == resident["quality"]["bpp_estimated"]
     assert streamed["quality"]["psnr_db"] == resident["quality"]["psnr_db"]
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run times the headline steps only (no `strong`, CPU-baseline, roofline or parity blocks: those are --full), reports
+    ms_per_step for exactly --steps steps, and --dump-outputs writes what the last step computed: the R-D records the line's
+    `quality` is made of and a fixed sample of the decoded B-frames, float32 / float64, well under 64 MB."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--gops-per-step", "1",
+                          "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    for key in ("strong", "cpu_baseline", "parity_vs_cpu", "roofline", "full_gop", "bitstream", "fp32_native"):
+        assert key not in line, key
+    rec = np.load(tmp_path / "rd_records.npy")
+    sample = np.load(tmp_path / "b_frames_sample.npy")
+    means = np.load(tmp_path / "b_frames_channel_mean.npy")
+    assert rec.dtype == np.float64 and rec.shape == (7, 6)
+    assert sample.dtype == np.float32 and sample.shape[0] == 7 and np.isfinite(sample).all()
+    assert means.dtype == np.float64 and means.shape == (7, 3) and np.isfinite(means).all()
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 * 2 ** 20
+    # the records are those `quality` summarises: mean PSNR, bits per pixel
+    assert abs(rec[:, 3].mean() - line["quality"]["psnr_db"]) < 1e-9
+    assert abs(rec[:, 4].sum() / rec[:, 5].sum() - line["quality"]["bpp_estimated"]) < 1e-12

@@ -1,5 +1,5 @@
 """The committed rocprofv3 evidence of the headline run (profiles/r06/, collected by tools/r06.sh headline on the MI355X box:
-`rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-strong-block --skip-extras --steps 3 --warmup 1`) is parsed
+`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-strong-block --skip-extras --steps 3 --warmup 1`) is parsed
 and held against the bench line printed by the SAME process:
 
   * no PyTorch operator kernel (`at::native`, elementwise / reduction / copy kernels of ATen) takes more than 0.1 % of the

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-3 bench lines on the MI355X box (run from the repo root through gpurun); one JSON line + kernel table per configuration.
 OUT=gpurun_out/final_r03; mkdir -p $OUT
-run() { name=$1; shift; python bench.py "$@" --kernel-table $OUT/kt_$name.json > $OUT/$name.json 2> $OUT/$name.err; tail -1 $OUT/$name.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],2), d['unit'], 'ms/step', round(d['ms_per_step'],1), d.get('conv_engine',{}).get('avg_tflops'))" || tail -3 $OUT/$name.err; }
+run() { name=$1; shift; python bench.py --full "$@" --kernel-table $OUT/kt_$name.json > $OUT/$name.json 2> $OUT/$name.err; tail -1 $OUT/$name.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],2), d['unit'], 'ms/step', round(d['ms_per_step'],1), d.get('conv_engine',{}).get('avg_tflops'))" || tail -3 $OUT/$name.err; }
 run lhbdc_fp32
 run lhbdc_fp16 --precision fp16 --no-cpu-baseline
 run icip_fp16 --model icip2024 --precision fp16 --no-cpu-baseline

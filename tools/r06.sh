@@ -5,7 +5,7 @@
 #   fp16-pmc             fp16-path kernels, matrix pipe + LDS side                        -> gpurun_out/prof_r06/pmc_fp16.json
 #   final                bench lines + kernel tables of every configuration               -> gpurun_out/final_r06/
 #   logs                 printed reports of the parity tests, ew_bench, suite durations, default bench line -> gpurun_out/logs_r06/
-#   all                  headline, split-pmc, final, then the default `python bench.py` line
+#   all                  headline, split-pmc, final (which ends with the `python bench.py --full` line)
 #   li-diag              two processes x the diagnostic variants of the level-input kernel (make li_diag; VARIANTS / REPS / ROUNDS)
 #   li-corun             variant 1 beside a torch tenant / tools/hammer.py / itself / alone (REPS)
 #   li-corun2            variant 1 beside a tenant of tiny torch kernels / of this library's short element-wise kernels / itself (REPS)
@@ -28,7 +28,7 @@ set -u
 OUT=gpurun_out/prof_r06
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-rocprofv3 --kernel-trace --stats -d $OUT/headline --output-format csv -- python3 bench.py --no-cpu-baseline --no-strong-block --skip-extras --steps 3 --warmup 1 > $OUT/a_headline_under_rocprofv3_line.json 2> $OUT/a_headline.err
+rocprofv3 --kernel-trace --stats -d $OUT/headline --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-strong-block --skip-extras --steps 3 --warmup 1 > $OUT/a_headline_under_rocprofv3_line.json 2> $OUT/a_headline.err
 python3 tools/trace_summary.py $OUT/headline $OUT/a_kernel_trace_by_grid.json
 cp $(find $OUT/headline -name "*kernel_stats.csv" | head -1) $OUT/a_rocprofv3_kernel_stats.csv
 find $OUT -name "*_kernel_trace.csv" -delete
@@ -111,7 +111,7 @@ PY
 final)
 # Round-6 bench lines on the MI355X box (run from the repo root through gpurun); one JSON line + kernel table per configuration.
 OUT=gpurun_out/final_r06; mkdir -p $OUT
-run() { name=$1; shift; python bench.py "$@" --kernel-table $OUT/kernel_table_$name.json > $OUT/bench_line_$name.json 2> $OUT/$name.err; tail -1 $OUT/bench_line_$name.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],2), d['unit'], 'ms/step', round(d['ms_per_step'],1), d.get('conv_engine',{}).get('timed_region_tflops'), d.get('hbm_kernels_ms_per_frame'))" || tail -3 $OUT/$name.err; }
+run() { name=$1; shift; python bench.py --full "$@" --kernel-table $OUT/kernel_table_$name.json > $OUT/bench_line_$name.json 2> $OUT/$name.err; tail -1 $OUT/bench_line_$name.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$name', round(d['value'],2), d['unit'], 'ms/step', round(d['ms_per_step'],1), d.get('conv_engine',{}).get('timed_region_tflops'), d.get('hbm_kernels_ms_per_frame'))" || tail -3 $OUT/$name.err; }
 run lhbdc_fp32 --no-cpu-baseline
 run flex_fp32 --model flex --no-cpu-baseline
 run flex_fp32_native --model flex --fp32-mode native --no-cpu-baseline
@@ -123,6 +123,7 @@ run icip_fp16 --model icip2024 --precision fp16 --no-cpu-baseline
 run icip_fp16_2160p --model icip2024 --precision fp16 --resolution 2160p --no-cpu-baseline
 run lhbdc_fp16_2160p --precision fp16 --resolution 2160p --no-cpu-baseline
 run lhbdc_fp32_2160p --resolution 2160p --no-cpu-baseline
+python bench.py --full > $OUT/h_bench_line_final.json 2> $OUT/h_bench.err
 ;;
 logs)
 # Round 6: the printed reports of the parity tests + the memory-bound kernels' micro-benchmark + the suite's durations + the default bench line
@@ -131,7 +132,7 @@ python -m pytest tests/test_byte_equality_gpu.py -q -s 2>&1 | grep -v "alone on 
 python -m pytest tests/test_reference_1080p_gpu.py tests/test_refine_gpu.py tests/test_bitstream_gpu.py "tests/test_fullsize_gpu.py::test_flex_1080p_against_oracle" -q -s 2>&1 | grep -v "alone on the oracle\|amdgpu.ids" | cut -c1-1500 > $O/e_reference_1080p_and_flex.log
 (echo "== shipped form (grid-stride over pixels)"; python tools/ew_bench.py --reps 30 2>&1 | grep -v amdgpu.ids; echo "== VC_LI_FORM=rows (opt-in)"; VC_LI_FORM=rows python tools/ew_bench.py --reps 30 2>&1 | grep level_input) > $O/g_ew_bench.log
 python -m pytest tests/ -q -m gpu --durations=25 2>&1 | tail -40 > $O/f_gpu_suite_durations.log
-python bench.py > $O/h_bench_line_final.json 2> $O/h_bench.err
+python bench.py --full > $O/h_bench_line_final.json 2> $O/h_bench.err
 tail -3 $O/e_byte_equality.log | cut -c1-300; grep -c "passed\|failed" $O/e_reference_1080p_and_flex.log; tail -2 $O/f_gpu_suite_durations.log; tail -c 600 $O/h_bench_line_final.json
 ;;
 li-diag)
@@ -289,15 +290,14 @@ python tools/conv_bench.py --precision fp16 --half-io --residual-half --reps 5 1
 ;;
 epilogue-ab)
 for i in 1 2; do
-VC_HIP_LIB=$OLD_LIB python bench.py --no-cpu-baseline --no-strong-block --skip-extras --steps 4 --warmup 1 2>/dev/null | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('other library ', round(d['value'],2), round(d['roofline']['avg_launch_ms'],3), d['conv_engine']['timed_region_tflops'])"
-python bench.py --no-cpu-baseline --no-strong-block --skip-extras --steps 4 --warmup 1 2>/dev/null | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('shipped library', round(d['value'],2), round(d['roofline']['avg_launch_ms'],3), d['conv_engine']['timed_region_tflops'])"
+VC_HIP_LIB=$OLD_LIB python bench.py --full --no-cpu-baseline --no-strong-block --skip-extras --steps 4 --warmup 1 2>/dev/null | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('other library ', round(d['value'],2), round(d['roofline']['avg_launch_ms'],3), d['conv_engine']['timed_region_tflops'])"
+python bench.py --full --no-cpu-baseline --no-strong-block --skip-extras --steps 4 --warmup 1 2>/dev/null | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('shipped library', round(d['value'],2), round(d['roofline']['avg_launch_ms'],3), d['conv_engine']['timed_region_tflops'])"
 done
 ;;
 all)
 bash tools/r06.sh headline > gpurun_out/prof_r06_headline.log 2>&1
 bash tools/r06.sh split-pmc > gpurun_out/prof_r06_split.log 2>&1
 bash tools/r06.sh final > gpurun_out/final_r06_summary.log 2>&1
-python bench.py > gpurun_out/final_r06/h_bench_line_final.json 2> gpurun_out/final_r06/h_bench.err
 tail -5 gpurun_out/prof_r06_headline.log | cut -c1-300; tail -12 gpurun_out/prof_r06_split.log | cut -c1-400; cat gpurun_out/final_r06_summary.log; tail -c 1500 gpurun_out/final_r06/h_bench_line_final.json
 ;;
 *) echo "usage: bash tools/r06.sh headline|split-pmc|fp16-pmc|final|logs|all|li-diag|li-corun|li-corun2|li-mix|li-vashift|two-process-spynet|two-process-forward|stamps|stamps-epilogue|f16-stamps|epilogue-ab"; exit 2;;
