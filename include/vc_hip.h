@@ -386,6 +386,19 @@ int vc_bits_slots(void);
  * channels in double, 10*log10(255^2/mse) -> *psnr_out (device).  scratch: vc_bits_slots() doubles (device). */
 int vc_psnr_uint8(vc_stream s, const float *a_chw, const float *b_chw, int channels, int H, int W, int h, int w,
                   double *scratch, int slots, double *psnr_out);
+/* MS-SSIM as pytorch-msssim's ms_ssim computes it with its default arguments (the definition is spelled out at the top of
+ * csrc/metrics.hip), on the images vc_psnr_uint8 sees: n pairs of CHW fp32 images (row pitch W, plane pitch H*W, image_pitch
+ * floats from one image to the next), [:h,:w] crop, quantize=1: rint(clamp(v,0,1)*255) like the PSNR kernel, quantize=0: v*255.
+ * Data range 255, 11-tap Gaussian window (sigma 1.5), five scales, window sums in fp64.  msssim_out: n doubles (device);
+ * terms_out (nullable): [n][5][channels] doubles, the per-scale terms after max(., 0) (cs of scales 0..3, ssim of scale 4).
+ * Six launches for any n, no atomics: the same input gives the same bits.  workspace: vc_msssim_workspace_bytes(n, channels, h, w)
+ * bytes on the device (pooled pyramids of both images + per-workgroup partials), 16-byte aligned; that function is host-only
+ * and returns 0 for sizes the metric refuses.  VC_EINVAL before any launch for null pointers, n < 1, channels < 1, h > H, w > W,
+ * min(h,w) <= 160, image_pitch < channels*H*W, quantize outside {0,1}, or a workspace that is too small. */
+size_t vc_msssim_workspace_bytes(int n, int channels, int h, int w);
+int vc_msssim(vc_stream s, const float *a, const float *b, int n, int channels, int H, int W, int h, int w,
+              long long image_pitch, int quantize, void *workspace, size_t workspace_bytes, double *terms_out,
+              double *msssim_out);
 
 /* ------------------------------------------------------------------------------------------
  * Range coder (host).  Replaces compressai._CXX.pmf_to_quantized_cdf and

@@ -6,7 +6,8 @@
 
 ``encode_B`` / ``decode_B`` mirror LHBDC/encode_B.py:21-28,108-126 and LHBDC/decode_B.py:23-28,88-124 (same argument
 names and defaults, same ``bits_B.bin`` container, ``decoded.png`` written beside the bitstream); ``test`` mirrors the
-argument parser and the loop of LHBDC/test/testing.py:35-59,89-196 on top of ``vcamd.data.SequenceReader``.
+argument parser and the loop of LHBDC/test/testing.py:35-59,89-196 on top of ``vcamd.data.SequenceReader``; ``test --msssim`` adds
+an MS-SSIM column (pytorch-msssim ``ms_ssim`` defaults on the same uint8 crops, computed on the device) to every line it prints.
 
 Checkpoints: ``--weights`` (default ``pretrained_weights/compression_<l>.pth``, as the reference) is loaded with
 ``torch.load(...)["state_dict"]``.  The reference's checkpoints live on Google Drive; where none is present ``--seeded
@@ -91,7 +92,7 @@ def cmd_decode_B(args):
 
 def cmd_test(args):
     """testing.py:65-196: every sequence under --test_path, GOP by GOP, I-frames through mbt2018_mean(--i_qual),
-    B-frames through the model; prints the per-level and overall (PSNR, bpp) table."""
+    B-frames through the model; prints the per-level and overall (PSNR, bpp) table (``--msssim``: with an MS-SSIM column)."""
     from vcamd import gop
     from vcamd.iframe import mbt2018_mean
     dev = _device()
@@ -107,22 +108,25 @@ def cmd_test(args):
     reader = SequenceReader(args.test_path, None, args.test_gop_size, args.test_skip_frames, args.test_numbers, dev, args.workers,
                             yuv_size=tuple(args.yuv_size) if args.yuv_size else None)
     table = gop.RdTable()
+
+    def ms(v):
+        return f"  MS-SSIM {v['msssim']:.4f}" if args.msssim else ""
     with torch.no_grad():
         for vi, name in enumerate(reader.video_names):
             avail = (len(reader.videos[vi]) + reader.skip_frames - 1) // reader.skip_frames
             reader.prefetch([k for k in reader.items if k[0] == vi])
             rows = gop.code_sequence_lhbdc(model, i_model, lambda idx, vi=vi: reader.load_frame(vi, idx), avail, reader.h, reader.w,
-                                           video=vi, gop_size=args.test_gop_size, test_size=args.test_numbers)
+                                           video=vi, gop_size=args.test_gop_size, test_size=args.test_numbers, msssim=args.msssim)
             rows = gop.gather_records(rows, dev)                 # one D2H of the per-frame scalars, (video, frame) order
             for r in rows.tolist():
-                table.update("I" if int(r[6]) == 1 else "B", r[1], int(r[2]), int(r[0]), r[3], r[4], r[5])
+                table.update("I" if int(r[6]) == 1 else "B", r[1], int(r[2]), int(r[0]), r[3], r[4], r[5], r[7] if args.msssim else None)
             s = gop.summarize(rows)
-            print(f"{name}: {s['frames']} frames  PSNR {s['psnr']:.3f} dB  {s['bpp']:.4f} bpp", flush=True)
+            print(f"{name}: {s['frames']} frames  PSNR {s['psnr']:.3f} dB  {s['bpp']:.4f} bpp{ms(s)}", flush=True)
     summary = {"per_level": table.per_level(), "per_level_frame_type": table.per_level_frame_type(),
                "overall": table._group(lambda r: 0).get(0)}
     for level, v in summary["per_level"].items():
-        print(f"level {level:2d}: {v['frames']:4d} frames  PSNR {v['psnr']:.3f} dB  {v['bpp']:.4f} bpp")
-    print(f"overall : {summary['overall']['frames']:4d} frames  PSNR {summary['overall']['psnr']:.3f} dB  {summary['overall']['bpp']:.4f} bpp")
+        print(f"level {level:2d}: {v['frames']:4d} frames  PSNR {v['psnr']:.3f} dB  {v['bpp']:.4f} bpp{ms(v)}")
+    print(f"overall : {summary['overall']['frames']:4d} frames  PSNR {summary['overall']['psnr']:.3f} dB  {summary['overall']['bpp']:.4f} bpp{ms(summary['overall'])}")
     st = reader.stats
     print(f"ingest: {st['frames']} frames, decode {st['decode_s']:.2f} s (worker time), H2D {st['h2d_s']:.2f} s, consumer waited "
           f"{st['wait_s']:.2f} s")
@@ -171,6 +175,7 @@ def build_parser():
     t.add_argument("--lmbda", type=int, default=1626)
     t.add_argument("--yuv_size", type=int, nargs=2, default=None, metavar=("W", "H"), help="sequences are raw 8-bit 4:2:0 files of this size")
     t.add_argument("--seeded", type=int, default=None)
+    t.add_argument("--msssim", action="store_true", help="also report MS-SSIM (pytorch-msssim ms_ssim defaults, data range 255) per sequence, level and overall")
     t.set_defaults(fn=cmd_test)
     return ap
 

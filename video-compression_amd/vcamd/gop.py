@@ -38,10 +38,24 @@ def psnr_uint8(x_hat, x, h, w):
     return hip.psnr_uint8(x_hat, x, h, w)
 
 
+def msssim_uint8(x_hat, x, h, w):
+    """MS-SSIM (pytorch-msssim ``ms_ssim`` defaults, data range 255) of the same uint8-rounded crop of the first image -- six HIP
+    launches (vc_msssim), result left on the device."""
+    from . import hip
+    return hip.msssim_uint8(x_hat[:1], x[:1], h, w)[0]
+
+
+def _record(video, frame, level, x_hat, x, h, w, bits, msssim, is_intra=0):
+    """One per-frame record: (video, frame, level, psnr, bits, pixels), or with ``msssim`` the one extended layout
+    (video, frame, level, psnr, bits, pixels, is_intra, msssim) that GOP-level and sequence-level loops share."""
+    rec = (video, frame, level, psnr_uint8(x_hat, x, h, w), bits, float(h * w))
+    return rec + (is_intra, msssim_uint8(x_hat, x, h, w)) if msssim else rec
+
+
 LEVEL_GROUPS = [[4], [2, 6], [1, 3, 5, 7]]                    # frames of one hierarchy level are independent
 
 
-def code_gop_lhbdc(model, gop, dec_first, dec_last, h, w, records=None, video=0, gop_index=0, batch_levels=True):
+def code_gop_lhbdc(model, gop, dec_first, dec_last, h, w, records=None, video=0, gop_index=0, batch_levels=True, msssim=False):
     """Code the 7 B-frames of one GOP-8.  ``gop``: list of 9 NCHW frames (padded), ``dec_first`` /
     ``dec_last``: decoded boundary frames.  Appends (video, frame, level, psnr, bits, pixels) to
     ``records`` in the reference's coding order (psnr and bits stay device scalars: no host sync inside
@@ -50,7 +64,10 @@ def code_gop_lhbdc(model, gop, dec_first, dec_last, h, w, records=None, video=0,
     ``batch_levels``: the frames of one hierarchy level ({4}, {2,6}, {1,3,5,7}) depend only on already
     decoded levels, so each level runs as ONE batched pass (1, 2, 4 frames) through the same kernels --
     identical per-frame arithmetic, but the small feature maps of the hyper-networks / MV codec / coarse
-    SPyNet levels get 2-4x more workgroups and the big layers lose their partial last wave."""
+    SPyNet levels get 2-4x more workgroups and the big layers lose their partial last wave.
+
+    ``msssim``: records get the extended layout (video, frame, level, psnr, bits, pixels, is_intra, msssim) -- MS-SSIM of the same
+    crop as a device scalar (:func:`msssim_uint8`); the default leaves the 6-field records as they are."""
     decoded = {0: dec_first, 8: dec_last}
     stats = {}
     groups = LEVEL_GROUPS if batch_levels else [[o] for o in CODING_ORDER[2:]]
@@ -65,12 +82,11 @@ def code_gop_lhbdc(model, gop, dec_first, dec_last, h, w, records=None, video=0,
             stats[o] = tot[i].sum()
     if records is not None:
         for order in CODING_ORDER[2:]:
-            records.append((video, gop_index * 8 + order, HIER_LEVELS[order],
-                            psnr_uint8(decoded[order], gop[order], h, w), stats[order], float(h * w)))
+            records.append(_record(video, gop_index * 8 + order, HIER_LEVELS[order], decoded[order], gop[order], h, w, stats[order], msssim))
     return decoded
 
 
-def code_gops_lhbdc(model, gops, bounds, h, w, records=None, video=0, first_gop_index=0):
+def code_gops_lhbdc(model, gops, bounds, h, w, records=None, video=0, first_gop_index=0, msssim=False):
     """Several independent GOP-8s in one go: GOPs share nothing but the model, so hierarchy level l of ALL of them runs
     as one batched pass (G, 2G, 4G frames) -- the same per-frame arithmetic as :func:`code_gop_lhbdc`, with the
     single-frame level {4} and the coarse layers getting G times more work per launch.  ``gops``: list of G lists of 9
@@ -92,15 +108,15 @@ def code_gops_lhbdc(model, gops, bounds, h, w, records=None, video=0, first_gop_
     if records is not None:
         for g in range(len(gops)):
             for order in CODING_ORDER[2:]:
-                records.append((video, (first_gop_index + g) * 8 + order, HIER_LEVELS[order],
-                                psnr_uint8(decoded[g][order], gops[g][order], h, w), stats[g][order], float(h * w)))
+                records.append(_record(video, (first_gop_index + g) * 8 + order, HIER_LEVELS[order], decoded[g][order], gops[g][order], h, w,
+                                       stats[g][order], msssim))
     return decoded
 
 
 LEVEL_GROUPS_16 = [[8], [4, 12], [2, 6, 10, 14], [1, 3, 5, 7, 9, 11, 13, 15]]
 
 
-def code_gops_flex(model, gops, bounds, h, w, quality, records=None, video=0, first_gop_index=0, batch_levels=True):
+def code_gops_flex(model, gops, bounds, h, w, quality, records=None, video=0, first_gop_index=0, batch_levels=True, msssim=False):
     """The 15 B-frames of each of several independent GOP-16s with the per-hierarchy-level (n, l) of ``quality`` (an entry
     of FLEX_QUALITIES or a plain {level: (n, l)} dict), like Flex-Rate.../test/testing.py:192-201.
     ``batch_levels``: the frames of one hierarchy level share their rate point and depend only on lower levels, so each
@@ -126,14 +142,14 @@ def code_gops_flex(model, gops, bounds, h, w, quality, records=None, video=0, fi
     if records is not None:
         for g in ng:
             for order in CODING_ORDER_16[2:]:
-                records.append((video, (first_gop_index + g) * 16 + order, HIER_LEVELS_16[order],
-                                psnr_uint8(decoded[g][order], gops[g][order], h, w), stats[g][order], float(h * w)))
+                records.append(_record(video, (first_gop_index + g) * 16 + order, HIER_LEVELS_16[order], decoded[g][order], gops[g][order], h, w,
+                                       stats[g][order], msssim))
     return decoded
 
 
-def code_gop_flex(model, gop, dec_first, dec_last, h, w, quality, records=None, video=0, gop_index=0, batch_levels=True):
+def code_gop_flex(model, gop, dec_first, dec_last, h, w, quality, records=None, video=0, gop_index=0, batch_levels=True, msssim=False):
     """One GOP-16 (see :func:`code_gops_flex`); returns its decoded dict."""
-    return code_gops_flex(model, [gop], [(dec_first, dec_last)], h, w, quality, records, video, gop_index, batch_levels)[0]
+    return code_gops_flex(model, [gop], [(dec_first, dec_last)], h, w, quality, records, video, gop_index, batch_levels, msssim)[0]
 
 
 # ICIP2024 GOP-16 (ICIP2024/src/utils.py:188-221, src/test.py:37-101): frame 16 is intra-coded first, then the
@@ -164,7 +180,7 @@ def icip2024_gop_plan(batch_levels=True, max_batch=8):
 
 
 def code_gop_icip2024(model, gop, dec_first, dec_last, h, w, level, records=None, video=0, gop_index=0,
-                      search="device", down_ratio=1, cache_features=True, batch_levels=True, max_batch=None):
+                      search="device", down_ratio=1, cache_features=True, batch_levels=True, max_batch=None, msssim=False):
     """Code the 15 B-frames of one ICIP2024 GOP-16 at quality ``level`` (0..4, fractional values interpolate the
     gain vectors), following src/test.py:37-101.
 
@@ -241,8 +257,7 @@ def code_gop_icip2024(model, gop, dec_first, dec_last, h, w, level, records=None
                     feats[o] = [f.images(i, i + 1) for f in batch_feats]
     if records is not None:
         for o in ICIP_ORDER_16[1:]:
-            records.append((video, gop_index * 16 + o, ICIP_LEVELS_16[o], psnr_uint8(decoded[o], gop[o], h, w), stats[o],
-                            float(h * w)))
+            records.append(_record(video, gop_index * 16 + o, ICIP_LEVELS_16[o], decoded[o], gop[o], h, w, stats[o], msssim))
     return decoded, picked
 
 
@@ -299,14 +314,15 @@ class GopGraph:
     (7 B-frames for LHBDC GOP-8, 15 for Flex GOP-16) captures into one graph: static input slots for the
     frames, intermediates in the graph's private pool, per-frame PSNR/bits left in static device tensors."""
 
-    def __init__(self, model, h, w, video=0, kind="lhbdc", quality=None, pool=None, gops=1):
+    def __init__(self, model, h, w, video=0, kind="lhbdc", quality=None, pool=None, gops=1, msssim=False):
         """``pool``: a torch.cuda.graph_pool_handle() shared by several GopGraphs that are replayed one after the
         other (e.g. one per quality level): their intermediates then reuse the same memory, and the tensors a
         replay returns are only valid until the next replay of ANY graph of the pool.
         ``gops`` (LHBDC, Flex-Rate): number of consecutive GOPs coded per replay with their level passes batched together
-        (:func:`code_gops_lhbdc`, :func:`code_gops_flex`); ``code`` then takes the frames of those GOPs in order."""
+        (:func:`code_gops_lhbdc`, :func:`code_gops_flex`); ``code`` then takes the frames of those GOPs in order.
+        ``msssim``: the captured graph also fills a static ``out_msssim`` and ``code`` appends the extended 8-field records."""
         self.model, self.h, self.w, self.video, self.kind, self.quality = model, h, w, video, kind, quality
-        self.pool, self.gops = pool, int(gops)
+        self.pool, self.gops, self.msssim = pool, int(gops), bool(msssim)
         if self.gops != 1 and kind == "icip2024":
             raise ValueError("multi-GOP graphs exist for the LHBDC and Flex-Rate coders")
         self.orders = {"lhbdc": CODING_ORDER[2:], "flex": CODING_ORDER_16[2:], "icip2024": ICIP_ORDER_16[1:]}[kind]
@@ -314,27 +330,28 @@ class GopGraph:
         self.span = 8 if kind == "lhbdc" else 16
         self.graph = None
         self.static_in = None
-        self.out_psnr = self.out_bits = None
+        self.out_psnr = self.out_bits = self.out_msssim = None
         self.decoded = None
 
     def _run(self, frames):
         recs = []
         if self.kind == "lhbdc" and self.gops > 1:
             gops = [frames[9 * g:9 * g + 9] for g in range(self.gops)]
-            dec = code_gops_lhbdc(self.model, gops, [(gp[0], gp[8]) for gp in gops], self.h, self.w, recs, self.video, 0)
+            dec = code_gops_lhbdc(self.model, gops, [(gp[0], gp[8]) for gp in gops], self.h, self.w, recs, self.video, 0, msssim=self.msssim)
         elif self.kind == "lhbdc":
-            dec = code_gop_lhbdc(self.model, frames, frames[0], frames[8], self.h, self.w, recs, self.video, 0)
+            dec = code_gop_lhbdc(self.model, frames, frames[0], frames[8], self.h, self.w, recs, self.video, 0, msssim=self.msssim)
         elif self.kind == "icip2024":       # quality = level; flow-resolution search on the device
             dec, _ = code_gop_icip2024(self.model, frames, frames[0], frames[16], self.h, self.w, self.quality, recs,
-                                       self.video, 0, search="device")
+                                       self.video, 0, search="device", msssim=self.msssim)
         elif self.gops > 1:
             gops = [frames[17 * g:17 * g + 17] for g in range(self.gops)]
-            dec = code_gops_flex(self.model, gops, [(gp[0], gp[16]) for gp in gops], self.h, self.w, self.quality, recs, self.video, 0)
+            dec = code_gops_flex(self.model, gops, [(gp[0], gp[16]) for gp in gops], self.h, self.w, self.quality, recs, self.video, 0,
+                                 msssim=self.msssim)
         else:
-            dec = code_gop_flex(self.model, frames, frames[0], frames[16], self.h, self.w, self.quality, recs, self.video, 0)
+            dec = code_gop_flex(self.model, frames, frames[0], frames[16], self.h, self.w, self.quality, recs, self.video, 0, msssim=self.msssim)
         psnr = torch.stack([r[3] for r in recs])
         bits = torch.stack([r[4] for r in recs])
-        return dec, psnr, bits
+        return dec, psnr, bits, (torch.stack([r[7] for r in recs]) if self.msssim else None)
 
     def code(self, frames, gop_index=0, records=None):
         """frames: the GOP's padded NCHW device tensors (boundary frames taken as decoded I-frames)."""
@@ -348,7 +365,7 @@ class GopGraph:
                 # thread_local: only THIS thread's calls are checked against the capture -- a process-group watchdog
                 # thread polling events (multi-GPU runs) must not invalidate it
                 with torch.cuda.graph(g, pool=self.pool, capture_error_mode="thread_local"):
-                    self.decoded, self.out_psnr, self.out_bits = self._run(self.static_in)
+                    self.decoded, self.out_psnr, self.out_bits, self.out_msssim = self._run(self.static_in)
             self.graph = g
         for dst, src in zip(self.static_in, frames):
             if dst.data_ptr() != src.data_ptr():
@@ -358,8 +375,9 @@ class GopGraph:
             for i in range(len(self.orders) * self.gops):
                 g, order = divmod(i, len(self.orders))
                 order = self.orders[order]
-                records.append((self.video, (gop_index + g) * self.span + order, self.levels[order], self.out_psnr[i].clone(),
-                                self.out_bits[i].clone(), float(self.h * self.w)))
+                rec = (self.video, (gop_index + g) * self.span + order, self.levels[order], self.out_psnr[i].clone(),
+                       self.out_bits[i].clone(), float(self.h * self.w))
+                records.append(rec + (0, self.out_msssim[i].clone()) if self.msssim else rec)
         return self.decoded
 
 
@@ -373,7 +391,8 @@ def shard_gops(num_gops, world_size, rank):
 def gather_records(records, device, width=None):
     """All-gather per-frame R-D records over the default process group (RCCL on GPUs, gloo on CPU) and
     return them sorted in (video, frame) order on every rank.  Payload is a few KB: latency-bound.
-    Records are (video, frame, level, psnr, bits, pixels) or, from the sequence loops, the same + is_intra; a rank
+    Records are (video, frame, level, psnr, bits, pixels), from the sequence loops the same + is_intra, or with MS-SSIM
+    the same + is_intra + msssim; a rank
     without records (more ranks than GOPs) passes ``width`` or takes part with the 7-column layout."""
     import torch.distributed as dist
     if width is None:
@@ -414,15 +433,21 @@ def gather_records(records, device, width=None):
 
 
 def summarize(rows):
-    """bpp = sum(bits)/sum(pixels); PSNR = mean of per-frame PSNR (utils.py:425-426), summed in frame order."""
+    """bpp = sum(bits)/sum(pixels); PSNR = mean of per-frame PSNR (utils.py:425-426), summed in frame order.  Rows with the
+    eighth column (MS-SSIM records) add "msssim", the mean of the per-frame values like PSNR."""
     if rows.numel() == 0:
         return {"frames": 0, "bpp": math.nan, "psnr": math.nan}
-    bits, pix, ps = 0.0, 0.0, 0.0
+    bits, pix, ps, ms = 0.0, 0.0, 0.0, 0.0
     for r in rows.tolist():
         ps += r[3]
         bits += r[4]
         pix += r[5]
-    return {"frames": int(rows.shape[0]), "bpp": bits / pix, "psnr": ps / rows.shape[0]}
+        if len(r) > 7:
+            ms += r[7]
+    out = {"frames": int(rows.shape[0]), "bpp": bits / pix, "psnr": ps / rows.shape[0]}
+    if rows.shape[1] > 7:
+        out["msssim"] = ms / rows.shape[0]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -448,12 +473,15 @@ def gop_batches(indices, gop_size=8):
 
 
 def code_sequence_lhbdc(b_model, i_model, load_frame, num_available, h, w, video=0, gop_size=8, test_size=2,
-                        gop_range=None, runner=None):
+                        gop_range=None, runner=None, msssim=False):
     """testing.py:125-188 for one video: I-frame 0 once, I-frame at the end of every GOP, 7 B-frames between.
     ``load_frame(idx)`` returns the padded NCHW device tensor of source frame ``idx``.  ``gop_range=(lo,hi)``
     restricts to a shard of GOPs (multi-GPU): a shard that does not start at GOP 0 re-codes its first
     boundary I-frame itself (intra frames do not depend on neighbours) but does not record it again.
-    Returns records (video, frame_num, level|-1 for I, psnr, bits, pixels, is_intra)."""
+    Returns records (video, frame_num, level|-1 for I, psnr, bits, pixels, is_intra); with ``msssim`` (a ``runner`` must have been
+    built with the same setting) every record carries MS-SSIM as an eighth field."""
+    if runner is not None and bool(getattr(runner, "msssim", False)) != bool(msssim):
+        raise ValueError("runner and code_sequence_lhbdc disagree on msssim")
     batches = gop_batches(uvg_frame_indices(num_available, gop_size, test_size), gop_size)
     lo, hi = gop_range if gop_range is not None else (0, len(batches))
     records = []
@@ -462,7 +490,7 @@ def code_sequence_lhbdc(b_model, i_model, load_frame, num_available, h, w, video
         x = load_frame(idx)
         x_hat, tot = i_model.forward_device(x)
         if record:
-            records.append((video, idx, -1, psnr_uint8(x_hat, x, h, w), tot.sum(), float(h * w), 1))
+            records.append(_record(video, idx, -1, x_hat, x, h, w, tot.sum(), msssim, 1) + (() if msssim else (1,)))
         return x_hat
 
     dec_last = None
@@ -476,8 +504,8 @@ def code_sequence_lhbdc(b_model, i_model, load_frame, num_available, h, w, video
             frames = [dec_first] + gop[1:-1] + [dec_last]
             runner.code(frames, gop_index=g, records=recs)
         else:
-            code_gop_lhbdc(b_model, gop, dec_first, dec_last, h, w, recs, video, g)
-        records.extend(r + (0,) for r in recs)
+            code_gop_lhbdc(b_model, gop, dec_first, dec_last, h, w, recs, video, g, msssim=msssim)
+        records.extend(r + (0,) if len(r) == 6 else r for r in recs)
     return records
 
 
@@ -500,7 +528,8 @@ def code_workload(plan, world_size, rank, intra, code_gops, gops_per_pass=1):
     a GOP needs only its two boundary I-frames, and intra frames depend on nothing, so a shard that starts inside a
     video codes that boundary frame itself (it is RECORDED by the rank that owns the GOP it closes).
 
-    ``intra(video, frame_idx) -> (decoded, record_tail)`` codes one I-frame; ``record_tail`` = (psnr, bits, pixels).
+    ``intra(video, frame_idx) -> (decoded, record_tail)`` codes one I-frame; ``record_tail`` = (psnr, bits, pixels) or, with MS-SSIM,
+    (psnr, bits, pixels, msssim); ``code_gops`` may then return the extended 8-field records, which pass through unchanged.
     ``code_gops(items, bounds) -> records`` codes the B-frames of up to ``gops_per_pass`` GOPs in one batched pass:
     ``items`` = plan entries, ``bounds`` = per GOP (decoded first, decoded last); returns 6-field records
     (video, frame, level, psnr, bits, pixels) with frame = gop_in_video * gop_size + order.
@@ -508,10 +537,14 @@ def code_workload(plan, world_size, rank, intra, code_gops, gops_per_pass=1):
     lo, hi = shard_gops(len(plan), world_size, rank)
     records, batch, prev = [], [], None
 
+    def intra_record(video, idx, tail):
+        tail = tuple(tail)
+        return (video, idx, -1) + tail[:3] + (1,) + tail[3:]
+
     def flush():
         if batch:
             recs = code_gops([b[0] for b in batch], [(b[1], b[2]) for b in batch])
-            records.extend(tuple(r) + (0,) for r in recs)
+            records.extend(tuple(r) + (0,) if len(r) == 6 else tuple(r) for r in recs)
             batch.clear()
 
     for k in range(lo, hi):
@@ -521,9 +554,9 @@ def code_workload(plan, world_size, rank, intra, code_gops, gops_per_pass=1):
         else:
             dec_first, tail = intra(video, idxs[0])
             if g == 0:                            # frame 0 of a video belongs to its first GOP
-                records.append((video, idxs[0], -1) + tuple(tail) + (1,))
+                records.append(intra_record(video, idxs[0], tail))
         dec_last, tail = intra(video, idxs[-1])
-        records.append((video, idxs[-1], -1) + tuple(tail) + (1,))
+        records.append(intra_record(video, idxs[-1], tail))
         batch.append((plan[k], dec_first, dec_last))
         if len(batch) == gops_per_pass:
             flush()
@@ -536,14 +569,16 @@ class LhbdcWorkloadCoder:
     """The two callbacks of :func:`code_workload` on the HIP path: mbt2018_mean I-frames + LHBDC B-frames, ``G`` GOPs per
     pass with their hierarchy levels batched (one HIP graph per pass size when ``graph``)."""
 
-    def __init__(self, b_model, i_model, load_frame, h, w, graph=True):
+    def __init__(self, b_model, i_model, load_frame, h, w, graph=True, msssim=False):
         self.b_model, self.i_model, self.load_frame, self.h, self.w, self.graph = b_model, i_model, load_frame, h, w, graph
+        self.msssim = bool(msssim)     # records and intra tails carry MS-SSIM (the extended layout)
         self.runners = {}
 
     def intra(self, video, idx):
         x = self.load_frame(video, idx)
         x_hat, tot = self.i_model.forward_device(x)
-        return x_hat, (psnr_uint8(x_hat, x, self.h, self.w), tot.sum(), float(self.h * self.w))
+        tail = (psnr_uint8(x_hat, x, self.h, self.w), tot.sum(), float(self.h * self.w))
+        return x_hat, tail + (msssim_uint8(x_hat, x, self.h, self.w),) if self.msssim else tail
 
     def code_gops(self, items, bounds):
         recs = []
@@ -551,7 +586,7 @@ class LhbdcWorkloadCoder:
         if self.graph:
             g = len(items)
             if g not in self.runners:
-                self.runners[g] = GopGraph(self.b_model, self.h, self.w, gops=g)
+                self.runners[g] = GopGraph(self.b_model, self.h, self.w, gops=g, msssim=self.msssim)
             frames = []
             for gp, (first, last) in zip(gops, bounds):
                 frames += [first] + gp[1:-1] + [last]
@@ -562,15 +597,15 @@ class LhbdcWorkloadCoder:
                 out.append((video, gop_in_video * 8 + int(r[1]) % 8) + tuple(r[2:]))
             return out
         for (video, gop_in_video, _), gp, (first, last) in zip(items, gops, bounds):
-            code_gop_lhbdc(self.b_model, gp, first, last, self.h, self.w, recs, video, gop_in_video)
+            code_gop_lhbdc(self.b_model, gp, first, last, self.h, self.w, recs, video, gop_in_video, msssim=self.msssim)
         return recs
 
 
-def code_sequence_flex(b_model, i_models, load_frame, num_available, h, w, quality, video=0, gop_size=16, test_size=2):
+def code_sequence_flex(b_model, i_models, load_frame, num_available, h, w, quality, video=0, gop_size=16, test_size=2, msssim=False):
     """Flex-Rate.../test/testing.py:124-224 for one video and ONE operating point ``quality`` = (i_qual, {hierarchy level:
     (n, l)}) (an entry of FLEX_QUALITIES): intra frame 0 once and one at the end of every GOP through
     ``i_models[i_qual]``, the 15 B-frames between them with the (n, l) of their level (level-batched passes).
-    Returns records (video, frame_num, level|-1 for I, psnr, bits, pixels, is_intra) like code_sequence_lhbdc."""
+    Returns records (video, frame_num, level|-1 for I, psnr, bits, pixels, is_intra) like code_sequence_lhbdc (``msssim``: + MS-SSIM)."""
     i_model = i_models[quality[0]]
     batches = gop_batches(uvg_frame_indices(num_available, gop_size, test_size), gop_size)
     records = []
@@ -578,7 +613,7 @@ def code_sequence_flex(b_model, i_models, load_frame, num_available, h, w, quali
     def intra(idx):
         x = load_frame(idx)
         x_hat, tot = i_model.forward_device(x)
-        records.append((video, idx, -1, psnr_uint8(x_hat, x, h, w), tot.sum(), float(h * w), 1))
+        records.append(_record(video, idx, -1, x_hat, x, h, w, tot.sum(), msssim, 1) + (() if msssim else (1,)))
         return x_hat
 
     dec_last = None
@@ -587,8 +622,8 @@ def code_sequence_flex(b_model, i_models, load_frame, num_available, h, w, quali
         dec_first = dec_last if dec_last is not None else intra(idxs[0])
         dec_last = intra(idxs[-1])
         recs = []
-        code_gop_flex(b_model, gop, dec_first, dec_last, h, w, quality, recs, video, g)
-        records.extend(r + (0,) for r in recs)
+        code_gop_flex(b_model, gop, dec_first, dec_last, h, w, quality, recs, video, g, msssim=msssim)
+        records.extend(r + (0,) if len(r) == 6 else r for r in recs)
     return records
 
 
@@ -597,22 +632,31 @@ class RdTable:
     bpp = sum(size)/sum(pixels), grouped like print_per_level / per_video_level / per_frame_type."""
 
     def __init__(self):
-        self.rows = []   # (video, level, frame_num, frame_type, psnr, size, pixels)
+        self.rows = []   # (video, level, frame_num, frame_type, psnr, size, pixels[, msssim])
 
-    def update(self, frame_type, frame_num, level, video, psnr, size, pixels):
-        self.rows.append((video, level, int(frame_num), frame_type, float(psnr), float(size), float(pixels)))
+    def update(self, frame_type, frame_num, level, video, psnr, size, pixels, msssim=None):
+        row = (video, level, int(frame_num), frame_type, float(psnr), float(size), float(pixels))
+        self.rows.append(row if msssim is None else row + (float(msssim),))
 
     def extend_from_records(self, rows, level):
         for r in rows:
             intra = len(r) > 6 and int(r[6]) == 1
-            self.update("I" if intra else "B", r[1], level, int(r[0]), r[3], r[4], r[5])
+            self.update("I" if intra else "B", r[1], level, int(r[0]), r[3], r[4], r[5], r[7] if len(r) > 7 else None)
 
     def _group(self, key):
+        """``msssim`` (mean of the per-frame values) appears in a group only when every row of it carries the value."""
         out = {}
         for row in self.rows:
-            acc = out.setdefault(key(row), [0.0, 0.0, 0.0, 0])
+            acc = out.setdefault(key(row), [0.0, 0.0, 0.0, 0, 0.0, 0])
             acc[0] += row[4]; acc[1] += row[5]; acc[2] += row[6]; acc[3] += 1
-        return {k: {"psnr": v[0] / v[3], "bpp": v[1] / v[2], "frames": v[3]} for k, v in sorted(out.items())}
+            if len(row) > 7:
+                acc[4] += row[7]; acc[5] += 1
+        res = {}
+        for k, v in sorted(out.items()):
+            res[k] = {"psnr": v[0] / v[3], "bpp": v[1] / v[2], "frames": v[3]}
+            if v[5] == v[3]:
+                res[k]["msssim"] = v[4] / v[3]
+        return res
 
     def per_level(self):
         return self._group(lambda r: r[1])

@@ -183,6 +183,8 @@ def lib():
     sig("vc_bits_reduce", ci, vp, vp, ci, ci, vp)
     sig("vc_bits_slots", ci)
     sig("vc_psnr_uint8", ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp)
+    sig("vc_msssim_workspace_bytes", sz, ci, ci, ci, ci)
+    sig("vc_msssim", ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, cll, ci, vp, sz, vp, vp)
     sig("vc_gdn", ci, vp, View, vp, vp, ci, View, View)
     sig("vc_pad", ci, vp, View, View)
     sig("vc_pmf_to_quantized_cdf", ci, vp, ci, ci, vp)
@@ -203,7 +205,7 @@ EXPORTED_SYMBOLS = [
     "vc_spynet_preprocess", "vc_spynet_level_input", "vc_spynet_level_input_sp3", "vc_lhbdc_blend", "vc_flex_blend",
     "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar",
     "vc_attention_gate", "vc_sse_clamp01", "vc_select_flow", "vc_eb_forward", "vc_eb_dequant", "vc_gc_forward", "vc_gc_indexes", "vc_refine_scales",
-    "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
+    "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
     # the operator spellings of SURVEY.md 8(b), thin forwards (csrc/abi_aliases.cpp)
     "vc_gdn", "vc_spynet_level", "vc_pool", "vc_upsample", "vc_pad", "vc_blend", "vc_factorized_bits", "vc_gaussian_symbols",
@@ -944,6 +946,34 @@ def psnr_uint8(x_hat, x, h, w, out=None):
     check(lib().vc_psnr_uint8(stream(), a.data_ptr(), b.data_ptr(), a.shape[0], a.shape[1], a.shape[2], int(h), int(w),
                               scratch.data_ptr(), slots, out.data_ptr()), "vc_psnr_uint8")
     return out
+
+
+def msssim_uint8(x_hat, x, h, w, out=None, quantize=True, terms=False):
+    """MS-SSIM (pytorch-msssim's ``ms_ssim`` with its defaults, data range 255; csrc/metrics.hip) of every image pair of two NCHW
+    fp32 CUDA tensors on the [:h,:w] crop -- uint8-rounded like :func:`psnr_uint8` unless ``quantize=False`` (then v * 255).  All N
+    images are scored by one call (six launches); returns a float64 device tensor [N] (``out``: a float64 view of that shape to write
+    into) -- no host synchronisation, capturable.  ``terms=True``: returns (values, [N,5,C] per-scale terms after the clamp at 0)."""
+    if x_hat.dtype != torch.float32 or x.dtype != torch.float32 or not x_hat.is_cuda or not x.is_cuda:
+        raise VcError("msssim_uint8 takes fp32 CUDA tensors")
+    if x_hat.dim() != 4 or x.shape != x_hat.shape:
+        raise VcError("msssim_uint8: NCHW tensors of the same shape")
+    a, b = x_hat.contiguous(), x.contiguous()
+    n, c, H, W = a.shape
+    h, w = min(int(h), H), min(int(w), W)      # the loops slice [:h, :w]: a crop larger than the frame is the frame
+    if min(h, w) <= 160:
+        raise VcError("msssim_uint8: five scales with an 11-tap window need min(h, w) > 160")
+    nbytes = lib().vc_msssim_workspace_bytes(n, c, h, w)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float64, device=x.device)
+    elif out.dtype != torch.float64 or out.numel() != n or not out.is_contiguous() or out.device != x.device:
+        raise VcError("msssim_uint8: out is a contiguous float64 view with one element per image")
+    t = torch.empty((n, 5, c), dtype=torch.float64, device=x.device) if terms else None
+    timed_hbm(f"k_msssim c{c} @{n}x{h}x{w}", 8.0 * n * c * h * w,
+              lambda: check(lib().vc_msssim(stream(), a.data_ptr(), b.data_ptr(), n, c, H, W, h, w, c * H * W, int(bool(quantize)),
+                                            workspace.data_ptr(), nbytes, None if t is None else t.data_ptr(), out.data_ptr()),
+                            "vc_msssim"))
+    return (out, t) if terms else out
 
 
 def nchw_frames_to_nhwc(frames, out=None):
