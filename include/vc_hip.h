@@ -334,7 +334,9 @@ int vc_eb_dequant(vc_stream s, const int32_t *symbols, const float *params, cons
 /* GaussianConditional.forward (eval) on y with (scales, means) = chunk(h_s output, 2):
  *   y_hat = (round(y*gain - mu) + mu) * out_gain ; p = Phi((.5-|v|)/s) - Phi((-.5-|v|)/s), s>=0.11, p>=1e-9.
  * sym_src (nullable) lets Flex's compress() quantise the UN-gained y (layers.py:167): symbols are
- * round(sym_src - mu) when given, else round(y*gain - mu).  indexes (nullable, needs scale_table) =
+ * round(sym_src - mu) when given, else round(y*gain - mu).  sym_src_p has NO view of its own: it is addressed with y's strides
+ * from y's base layout -- the element (n,iy,ix,c) is read at sym_src_p[n*y.sn + iy*y.sh + ix*y.sw + c], so it must point at a tensor
+ * (or window) of exactly y's shape and strides; needs `symbols`.  indexes (nullable, needs scale_table) =
  * build_indexes(scales) against scale_table[n_scales].  likelihoods (nullable, fp32, dense NCHW order like
  * symbols) receives out["likelihoods"]["y"]. */
 int vc_gc_forward(vc_stream s, vc_view y, vc_view scales, vc_view means, const float *in_gain,

@@ -686,6 +686,17 @@ class MeanScaleHyperprior(_Prepared):
             z = run_sequential(self.h_a, y, self._cache["h_a"])
         return y, y_raw, z, y_layer, z_layer
 
+    @staticmethod
+    def _check_sym_src_layout(y, y_raw):
+        """vc_gc_forward takes sym_src as a bare pointer and reads it at the element offsets of y's view (include/vc_hip.h): the
+        un-gained latent must have y's shape and strides."""
+        if y_raw is None:
+            return
+        if (y_raw.n, y_raw.h, y_raw.w, y_raw.c) != (y.n, y.h, y.w, y.c) or (y_raw.sn, y_raw.sh, y_raw.sw) != (y.sn, y.sh, y.sw):
+            raise hip.VcError("vc_gc_forward reads sym_src with y's strides: the un-gained latent "
+                              f"[{y_raw.n},{y_raw.h},{y_raw.w},{y_raw.c}] strides ({y_raw.sn},{y_raw.sh},{y_raw.sw}) is not laid out like y "
+                              f"[{y.n},{y.h},{y.w},{y.c}] strides ({y.sn},{y.sh},{y.sw})")
+
     def _quantise_for_bitstream(self, y, y_raw, z, y_layer, z_layer, gains, want_y_hat, counters=None):
         """Hyper-latent symbols -> z_hat -> (scales, means) -> latent symbols and scale-table indexes, with the boundary cases of both
         roundings decided in fp64 (hip.SYMBOL_REFINE).  Returns (z_sym [n, count], y_sym, y_idx, y_hat or None, (hz, wz)); device
@@ -709,6 +720,7 @@ class MeanScaleHyperprior(_Prepared):
         y_sym = torch.empty((y.n, y.c * y.h * y.w), dtype=torch.int32, device=dev)
         y_idx = torch.empty_like(y_sym)
         table = self._scale_table_dev()
+        self._check_sym_src_layout(y, y_raw)
         hip.check(L.vc_gc_forward(hip.stream(), y.view(), scales.view(), means.view(), None, None if ig is None else ig.data_ptr(),
                                   hip.NULL_VIEW if y_hat is None else y_hat.view(), None, 0, None if y_raw is None else y_raw.ptr,
                                   y_sym.data_ptr(), y_idx.data_ptr(), table.data_ptr(), table.numel(), None), "vc_gc_forward")
