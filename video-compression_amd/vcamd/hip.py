@@ -3,8 +3,10 @@
 This is the only door to the compute path: there is NO CPU fallback.  If the library is missing the
 import of any model module fails loudly with instructions to build it.
 """
+import collections
 import contextlib
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -345,6 +347,8 @@ def frame_to_uint8(x_nchw, h, w):
 # ------------------------------------------------------------------------------------------------
 # convolution
 # ------------------------------------------------------------------------------------------------
+# tile configurations: the enum of include/vc_hip.h under the same names
+CFG_N128, CFG_N64, CFG_N32, CFG_N16, CFG_N4, CFG_N128B, CFG_PW, CFG_N32T16 = range(8)
 CFG_EXACT = 0x100
 CFG_F16 = 0x200
 CFG_IN_F16 = 0x400
@@ -440,14 +444,47 @@ def fp32_mode_pinned(mode):
 
 
 def wants_split_at(pc, n, h, w):
-    return _FP32_MODE == "split" and pc is not None and pc.split_ok and pc.cin_split == pc.cin and pc.split_pays(n, h, w)
+    """Will the layer ``pc`` run on the split-operand pipeline for n images of h x w?  The hint a producer needs to leave its result
+    as a split tensor (``out_sp3``)."""
+    return _FP32_MODE == "split" and pc is not None and pc.split_ok and pc.cin_split == pc.cin and pc.split_pays(n, h, w)     # (a producer cannot write padding channels)
 
 
-def wants_split(pc, x, h=None, w=None):
-    """Will the layer ``pc`` run on the split-operand pipeline for an input of x's batch at h x w (default: x's own size)?  The hint
-    a producer needs to leave its result as a split tensor (``out_sp3``)."""
-    return (_FP32_MODE == "split" and pc is not None and pc.split_ok and pc.cin_split == pc.cin      # (a producer cannot write padding channels)
-            and pc.split_pays(x.n, x.h if h is None else h, x.w if w is None else w))
+def wants_split(pc, x, h=None, w=None, _at=wants_split_at):
+    """wants_split_at for an input of x's batch at h x w (default: x's own size).  (Bound to the predicate itself: replacing the module
+    attribute ``wants_split_at`` redirects the call sites that name it, not this function's.)"""
+    return _at(pc, x.n, x.h if h is None else h, x.w if w is None else w)
+
+
+SplitGeometry = collections.namedtuple("SplitGeometry", "served chunk cin_split bn ntw cpl th period")      # see split_geometry
+# What PackedConv._route decides: ``split``: the split-operand pipeline (else the classic one); ``out_dtype`` of the result; ``flags``:
+# the VC_CFG_* flag bits; ``cfg``: the whole word where the configuration is forced; ``key``: of PackedConv.tuned (None: not consulted)
+Route = collections.namedtuple("Route", "split out_dtype flags cfg key")
+
+
+@functools.lru_cache(maxsize=None)
+def _split_padded():
+    """VC_SPLIT_PADDED=1 (first name VC_SPLIT3_PADDED): the per-chunk padded split instances for every layer.  Read ONCE per process,
+    like split_period() of csrc/conv_split.hip: packing and every later launch must agree on the choice."""
+    return any(os.environ.get(name, "")[:1] not in ("", "0") for name in ("VC_SPLIT_PADDED", "VC_SPLIT3_PADDED"))
+
+
+def split_geometry(k, cout, cin):
+    """The split-operand instance of a k x k layer -- this side's one statement of what csrc/conv_split.hip (split_cpl, split_block,
+    split_period, ``th`` of conv_dispatch_split) and vc_conv_chunk(VC_CFG_SPLIT) decide.  ``served``: an instance exists (stride 1 is
+    the caller's business); ``chunk``: input channels per chunk of ``cpl`` planes of 8, ``cin_split``: cin padded to it; ``bn``: output
+    channels per workgroup = ``ntw`` N-tiles of 16; ``th``: rows of a 32-pixel tile; ``period``: the two-chunks-per-period instance."""
+    cpl = 2 if k == 3 else 1
+    chunk = 8 * cpl
+    cin_split = (cin + chunk - 1) // chunk * chunk
+    bn = 64 if cout % 64 == 0 else (32 if cout % 32 == 0 else 16)
+    served = (k in (3, 5) and bn >= 32) or (k == 7 and cout % 16 == 0)
+    th = 12 if k == 3 else (24 if bn == 16 else 16)
+    return SplitGeometry(served, chunk, cin_split, bn, bn // 16, cpl, th, bn > 16 and cin_split % (2 * chunk) == 0 and not _split_padded())
+
+
+def _vec16(t):
+    """an fp32 window the split pipeline can touch in 16-byte groups (split windows are always aligned)"""
+    return t is None or t.dtype == "sp3" or (t.dtype == "f32" and t.ptr % 16 == 0 and t.sn % 4 == 0 and t.sh % 4 == 0 and t.sw % 4 == 0)
 
 
 def split3(x, out=None, c_out=None):
@@ -508,10 +545,9 @@ class PackedConv:
         self._wsplit = None
         # input channels are padded to the chunk of the split instance (8 for 5x5 / 7x7, 16 for 3x3) with zero weights: first layers
         # with 6 channels (LHBDC mask U-Net, Flex-Rate U-Net) run on the split pipeline behind vc_split3_pad
-        chunk = 16 if kh == 3 else 8
-        self.cin_split = (cin + chunk - 1) // chunk * chunk
-        split_shape = stride == 1 and ((kh in (5, 7) and (cout % 32 == 0 or (kh == 7 and cout % 16 == 0)) and not pixelshuffle) or
-                                       (kh == 3 and cout % 32 == 0))
+        self._split = split_geometry(kh, cout, cin)
+        self.cin_split = self._split.cin_split
+        split_shape = self._split.served and stride == 1 and not (pixelshuffle and kh != 3)
         if split_shape and self.cin_split != cin:
             wpad = np.zeros((cout, self.cin_split, kh, kw), dtype=np.float32)
             wpad[:, :cin] = wnp.reshape(cout, cin, kh, kw)
@@ -521,18 +557,19 @@ class PackedConv:
         self._raw = (wnp, bnp) if (_PRECISION == "fp16" and kh == 1 and stride == 1 and cout == cin and cin in (64, 128) and not pixelshuffle) else None
         self._device = device
         ck = L.vc_conv_chunk(self.cfg, kh, stride, cin)
-        self.candidates = [c for c in range(self.cfg, 3) if L.vc_conv_chunk(c, kh, stride, cin) == ck] if self.cfg <= 2 else []
-        if self.cfg == 0 and kh == 3 and stride == 1:
-            self.candidates.append(5)          # VC_CFG_N128B: 128-channel block with the waves arranged 2x2
+        self._pack128 = CFG_PACK128 if self.cfg == CFG_N128 else 0
+        self.candidates = [c for c in range(self.cfg, CFG_N32 + 1) if L.vc_conv_chunk(c, kh, stride, cin) == ck] if self.cfg <= CFG_N32 else []
+        if self.cfg == CFG_N128 and kh == 3 and stride == 1:
+            self.candidates.append(CFG_N128B)  # 128-channel block with the waves arranged 2x2
         if self.candidates and kh == 1 and stride == 1 and not self.ps and 32 <= cin <= 128 and cout <= 128 and cin % 8 == 0:
-            self.candidates.append(6)          # VC_CFG_PW: streaming 1x1 kernel (skipped by the tuner when the call is not eligible)
+            self.candidates.append(CFG_PW)     # streaming 1x1 kernel (skipped by the tuner when the call is not eligible)
             if cin % 32 == 0 and cout % 32 == 0 and os.environ.get("VC_PWS_KERNELS", "1") != "0":
-                self.candidates.append(CFG_PWS)  # VC_CFG_PWS: the same through per-wave LDS-DMA rings
+                self.candidates.append(CFG_PWS)  # the same through per-wave LDS-DMA rings
         if self.candidates and kh == 7 and stride == 1:
-            self.candidates.append(7)          # VC_CFG_N32T16: 16-row tiles (less halo per output)
+            self.candidates.append(CFG_N32T16) # 16-row tiles (less halo per output)
         # VC_CFG_DMA (fp16 path, half-precision input; the library refuses shapes it has no instance for): 32 / 64 output channels,
         # blocks of 128, or -- plain output on the N128 packing, which pads weights and bias to 128s -- a partly padded last block
-        dma_cout = cout in (32, 64) or cout % 128 == 0 or (cout >= 96 and cout % 4 == 0 and self.cfg == 0 and not self.ps)
+        dma_cout = cout in (32, 64) or cout % 128 == 0 or (cout >= 96 and cout % 4 == 0 and self.cfg == CFG_N128 and not self.ps)
         if (self.candidates and kh in (3, 7) and stride == 1 and cin % 32 == 0 and dma_cout
                 and os.environ.get("VC_DMA_KERNELS", "1") != "0"):
             self.candidates.append(CFG_DMA)
@@ -540,7 +577,7 @@ class PackedConv:
         # (7x7: 64 -> 32, 32 -> 64; 3x3: 64 / 128 / 256 input channels to 64 or a multiple of 128 output channels, pixel shuffle
         #  included -- the library declines what it has no instance for and the tuner skips it)
         f32_shape = ((kh == 7 and (cin, cout) in ((64, 32), (32, 64)) and not self.ps) or
-                     (kh == 3 and cin in (64, 128, 256) and (cout == 64 or cout % 128 == 0) and self.cfg in (0, 1)) or
+                     (kh == 3 and cin in (64, 128, 256) and (cout == 64 or cout % 128 == 0) and self.cfg in (CFG_N128, CFG_N64)) or
                      (kh == 3 and (cin, cout) == (32, 64) and not self.ps) or
                      (kh == 5 and (cin, cout) in ((96, 32), (192, 64), (32, 64)) and not self.ps))
         self.dma_f32 = (bool(self.candidates) and stride == 1 and f32_shape
@@ -550,18 +587,19 @@ class PackedConv:
         # every alternative must read THIS packing: same channel chunk (the zero padding of cin depends on it)
         self.candidates = [c for c in self.candidates if L.vc_conv_chunk(c, kh, stride, cin) == ck]
 
-    def _pick_cfg(self, d, key, flags=0):
-        if key in self.tuned:
-            return self.tuned[key]
-        if flags & CFG_RES_F16:                       # a half-precision residual: the streaming 1x1 kernel / the LDS-DMA 3x3 kernel
-            return (CFG_PWS if self.k == 1 else CFG_DMA) | CFG_EXACT | flags
-        cands = self.candidates
-        if flags & CFG_F16 and 5 in cands:
-            cands = [c for c in cands if c != 0]     # the 4x1 128-channel fp16 instance spills registers
+    def _pick_cfg(self, d, r):
+        """The configuration word of a route that leaves the choice to ``tuned`` / the tuner."""
+        if r.key in self.tuned:
+            return self.tuned[r.key]
+        if r.cfg is not None:
+            return r.cfg
+        flags, cands = r.flags | self._pack128, self.candidates
+        if flags & CFG_F16 and CFG_N128B in cands:
+            cands = [c for c in cands if c != CFG_N128]     # the 4x1 128-channel fp16 instance spills registers
         if not (flags & CFG_F16 and flags & CFG_IN_F16) and not (self.dma_f32 and not flags & CFG_F16):
             cands = [c for c in cands if c != CFG_DMA]   # the LDS-DMA pipeline copies pixels as they are: half tensors, or fp32 on its fp32 instances
-        if flags & CFG_OUT_SP3:
-            cands = [c for c in cands if c in (0, 1, 2, 3, 5, 7, CFG_PWS)]    # split output: the classic instances' and the streaming 1x1 kernel's epilogue
+        if flags & CFG_OUT_SP3:      # split output: the classic instances' and the streaming 1x1 kernel's epilogue
+            cands = [c for c in cands if c in (CFG_N128, CFG_N64, CFG_N32, CFG_N16, CFG_N128B, CFG_N32T16, CFG_PWS)]
         if not AUTOTUNE or len(cands) < 2 or torch.cuda.is_current_stream_capturing():
             return (cands[0] if cands else self.cfg) | flags
         best, best_ms = self.cfg, float("inf")
@@ -578,8 +616,8 @@ class PackedConv:
             ms = e0.elapsed_time(e1)
             if ms < best_ms:
                 best, best_ms = c, ms
-        self.tuned[key] = best | CFG_EXACT | flags
-        return self.tuned[key]
+        self.tuned[r.key] = best | CFG_EXACT | flags
+        return self.tuned[r.key]
 
     @property
     def split_ok(self):
@@ -590,9 +628,8 @@ class PackedConv:
         """The split pipeline walks 16 x 32-pixel tiles with one workgroup per CU: on coarse pyramid levels (few tiles) the native
         instances with their 8-row tiles and several workgroups per CU are faster.  Decided per IMAGE, never by the batch: a
         frame must get the same bits whether it is coded alone or in a level-batched pass."""
-        bn = 64 if self.cout % 64 == 0 else (32 if self.cout % 32 == 0 else 16)
-        th = 12 if self.k == 3 else (24 if bn == 16 else 16)
-        return ((h + th - 1) // th) * ((w + 31) // 32) * (self.cout // bn) >= 48
+        g = self._split
+        return ((h + g.th - 1) // g.th) * ((w + 31) // 32) * (self.cout // g.bn) >= 48
 
     def split_pack(self):
         if self._wsplit is None:
@@ -646,170 +683,143 @@ class PackedConv:
         (see VC_CFG_RES_F16 in include/vc_hip.h)."""
         return self.wpk16 is not None and (CFG_PWS in self.candidates or (self.k == 3 and self.stride == 1 and CFG_DMA in self.candidates))
 
-    def _call_split(self, x, out, act, slope, res, chscale, out_sp3, res_first, epi=EPI_NONE, mul=None, in_xform=IN_NONE, tail=None,
-                    out_f16=False):
-        """The layer on the split-operand pipeline.  ``x``: an fp32 window (converted here) or a split tensor left by the layer in
-        front; ``out_sp3``: leave the result as a split tensor for a split consumer."""
-        if epi != EPI_NONE or mul is not None or in_xform != IN_NONE or tail is not None or act >= ACT_SIGMOID:
-            raise VcError("the split-operand pipeline has plain / (Leaky)ReLU epilogues only: no GDN, multiplier, input transform, "
-                          "fused tail, sigmoid or clamp (a split tensor reached a layer that needs one)")
-        if out_f16 and out is None:
-            out_f16 = False            # (a hint, like on the native path: the result of a split layer stays fp32 / split)
-        if out is not None and out.dtype == "f16":
-            raise VcError("the split-operand pipeline stores fp32 or split tensors")
-        if not self.split_ok:
-            raise VcError("a split tensor reached a layer the split-operand pipeline does not serve")
-        if x.dtype == "sp3" and x.c != self.cin_split:
-            raise VcError("a split tensor must bring the layer's (padded) channel count")
-        xs = x if x.dtype == "sp3" else split3(x, c_out=self.cin_split)
+    def _route(self, x, out=None, act=ACT_NONE, slope=0.01, res=None, epi=EPI_NONE, mul=None, in_xform=IN_NONE, chscale=None,
+               out_f16=False, res_first=False, tail=None, out_sp3=False):
+        """Decide one call (the arguments of ``__call__``): pipeline, output dtype, flag word, forced configuration -- a Route.
+        Refuses what no kernel serves; allocates nothing and calls nothing in the library."""
         ho, wo, co = self.out_shape(x.h, x.w)
-        if out is None:
-            out = T.empty(x.n, ho, wo, co, x.buf.device, "sp3" if out_sp3 else "f32")
-        wsp, bsp = self.split_pack()
-        d = ConvDesc()
-        d.inp = xs.split_view()
-        d.out = out.split_view() if out.dtype == "sp3" else out.view()
-        d.wpk, d.bias = wsp.data_ptr(), bsp.data_ptr()
-        res_sp3 = res is not None and res.dtype == "sp3"
-        if res is not None:
-            if res.dtype == "f16":
+        plain = epi == EPI_NONE and in_xform == IN_NONE and act < ACT_SIGMOID and mul is None and tail is None
+        first = CFG_RES_FIRST if res_first else 0      # out = act(conv + res) instead of act(conv) + res
+        # the split-operand pipeline: a split tensor left by the layer in front, or an fp32 window (converted by __call__) where it pays
+        if x.dtype == "sp3" or (_FP32_MODE == "split" and self.split_ok and self.split_pays(x.n, x.h, x.w) and plain
+                                and (out is None or out.dtype != "f16") and _vec16(out) and _vec16(res) and co % 4 == 0
+                                and x.dtype == "f32" and x.c == self.cin and (self.cin_split != self.cin or (x.c % 8 == 0 and _vec16(x)))):
+            if not plain:
+                raise VcError("the split-operand pipeline has plain / (Leaky)ReLU epilogues only: no GDN, multiplier, input transform, "
+                              "fused tail, sigmoid or clamp (a split tensor reached a layer that needs one)")
+            if out is not None and out.dtype == "f16":
+                raise VcError("the split-operand pipeline stores fp32 or split tensors")
+            if not self.split_ok:
+                raise VcError("a split tensor reached a layer the split-operand pipeline does not serve")
+            if x.dtype == "sp3" and x.c != self.cin_split:
+                raise VcError("a split tensor must bring the layer's (padded) channel count")
+            if res is not None and res.dtype == "f16":
                 raise VcError("the split-operand pipeline adds fp32 or split residuals")
-            d.res, d.res_sn, d.res_sh, d.res_sw = (res.ptr, res.image_bytes, 0, 0) if res_sp3 else (res.ptr, res.sn, res.sh, res.sw)
-        if chscale is not None:
-            d.chscale = chscale.data_ptr()
-        d.kh = d.kw = self.k
-        d.stride = 1
-        d.act, d.slope = act, slope
-        d.out_mode = OUT_PIXELSHUFFLE2 if self.ps else OUT_PLAIN
-        d.cfg = (CFG_SPLIT | CFG_EXACT | CFG_IN_SP3 | (CFG_OUT_SP3 if out.dtype == "sp3" else 0) | (CFG_RES_FIRST if res_first else 0)
-                 | (CFG_RES_SP3 if res_sp3 else 0))
-        what = f"vc_conv2d_nhwc(split k={self.k},{self.cin}->{self.cout})"
-        if timer is None:
-            check(lib().vc_conv2d_nhwc(stream(), ctypes.byref(d)), what)
-        else:
-            flops = 2.0 * x.n * x.h * x.w * self.cout * self.cin * self.k * self.k       # (stride 1: one output position per input pixel)
-            key = f"conv k{self.k} s1 {self.cin}->{self.cout} @{x.n}x{x.h}x{x.w}"
-            nbytes = (x.n * x.h * x.w * self.cin * 6 + x.n * ho * wo * co * (6 if out.dtype == "sp3" else 4) + self.cout * self.cin * self.k * self.k * 6
-                      + (x.n * ho * wo * co * (6 if res_sp3 else 4) if res is not None else 0))
-            split_keys.add(key)
-            ntw = 4 if self.cout % 64 == 0 else (2 if self.cout % 32 == 0 else 1)
-            cpl, th = (2, 12) if self.k == 3 else (1, 24 if ntw == 1 else 16)
-            kernel_symbols[key] = f"conv_split_kernel<SplitCfg<{self.k}, {ntw}, {cpl}, {th},"
-            if (ntw > 1 and self.cin_split % (32 if self.k == 3 else 16) == 0 and os.environ.get("VC_SPLIT_PADDED", "0") in ("", "0")
-                    and os.environ.get("VC_SPLIT3_PADDED", "0") in ("", "0")):
-                kernel_symbols[key] = f"conv_split_period_kernel<SplitPeriodCfg<{self.k}, {ntw}, {th},"    # two chunks per period: less tap padding
-            timer.bracket(key, flops, lambda: check(lib().vc_conv2d_nhwc(stream(), ctypes.byref(d)), what), nbytes)
-        return out
-
-    def __call__(self, x, out=None, act=ACT_NONE, slope=0.01, res=None, epi=EPI_NONE, mul=None,
-                 in_xform=IN_NONE, chscale=None, out_f16=False, res_first=False, tail=None, out_sp3=False):
-        """``out_f16``: a hint that every consumer of the result is an fp16-path convolution (``half_ok``), so the
-        result may be stored as half (bit-identical downstream, half the traffic).  Honoured only when this layer
-        itself runs on the fp16 path and allocates its own output; otherwise the result stays fp32."""
-        ho, wo, co = self.out_shape(x.h, x.w)
-
-        def vec16(t):
-            """an fp32 window the split epilogue can touch in 16-byte groups (split windows are always aligned)"""
-            return t is None or t.dtype == "sp3" or (t.dtype == "f32" and t.ptr % 16 == 0 and t.sn % 4 == 0 and t.sh % 4 == 0 and t.sw % 4 == 0)
-        if x.dtype == "sp3" or (_FP32_MODE == "split" and self.split_ok and self.split_pays(x.n, x.h, x.w) and epi == EPI_NONE
-                                and in_xform == IN_NONE and act < ACT_SIGMOID
-                                and mul is None and tail is None and (out is None or out.dtype != "f16")
-                                and vec16(out) and vec16(res) and co % 4 == 0
-                                and x.dtype == "f32" and x.c == self.cin
-                                and (self.cin_split != self.cin or (x.c % 8 == 0 and x.sw % 4 == 0 and x.sh % 4 == 0 and x.sn % 4 == 0 and x.ptr % 16 == 0))):
-            return self._call_split(x, out, act, slope, res, chscale, out_sp3, res_first, epi, mul, in_xform, tail, out_f16)
+            # (``out_f16`` is a hint, like on the classic pipeline: the result of a split layer stays fp32 / split)
+            dt = out.dtype if out is not None else ("sp3" if out_sp3 else "f32")
+            flags = (CFG_IN_SP3 | (CFG_OUT_SP3 if dt == "sp3" else 0) | first | (CFG_RES_SP3 if res is not None and res.dtype == "sp3" else 0))
+            return Route(True, dt, flags, CFG_SPLIT | CFG_EXACT | flags, None)
         half_in = x.dtype == "f16"
         esz = 8 if half_in else 4
         use16 = (self.wpk16 is not None and in_xform == IN_NONE and x.sw % esz == 0 and x.sh % esz == 0 and x.sn % esz == 0
                  and x.ptr % 16 == 0)
         if half_in and not use16:
             raise VcError("a half-precision activation reached a layer that is not on the fp16 path")
-        # a split consumer behind a NATIVE fp32 layer (stride-2 / 1x1 / GDN / small-cin layers): the classic instances write the three
-        # bf16 pieces themselves (CFG_OUT_SP3); the streaming / LDS-DMA configurations do not, so the tuner is held to the classic ones
-        sp_out = (out.dtype == "sp3") if out is not None else bool(out_sp3 and _FP32_MODE == "split" and not use16 and co % 8 == 0
-                                                                    and self.cfg in (0, 1, 2, 3) and (res is None or res.dtype == "f32"))
         # fp16 mode: the fp32 GDN / IGDN instance of the streaming 1x1 kernel may STORE half (the input -- operand and identity -- of a
         # residual block that runs on the fp16 path; part of that mode's tolerance like every VC_HALF_RESIDUAL tensor)
         gdn_half_ok = (_PRECISION == "fp16" and HALF_ACTIVATIONS and HALF_RESIDUAL and epi != EPI_NONE and self.k == 1 and self.cin == 128
                        and self.cout == 128 and CFG_PWS in self.candidates and mul is x and x.dtype == "f32" and not res_first and chscale is None
                        and (res is None or res.dtype == "f32"))
-        if out is None:
-            out = T.empty(x.n, ho, wo, co, x.buf.device, "sp3" if sp_out else
-                          ("f16" if (out_f16 and HALF_ACTIVATIONS and (use16 or gdn_half_ok) and co % 4 == 0) else "f32"))
-        half_out = out.dtype == "f16"
+        # a split consumer behind a NATIVE fp32 layer (stride-2 / 1x1 / GDN / small-cin layers): the classic instances write the three
+        # bf16 pieces themselves (CFG_OUT_SP3); the streaming / LDS-DMA configurations do not, so the tuner is held to the classic ones
+        sp_hint = (out_sp3 and _FP32_MODE == "split" and not use16 and co % 8 == 0 and self.cfg in (CFG_N128, CFG_N64, CFG_N32, CFG_N16)
+                   and (res is None or res.dtype == "f32"))
+        dt = out.dtype if out is not None else ("sp3" if sp_hint else
+                                                ("f16" if (out_f16 and HALF_ACTIVATIONS and (use16 or gdn_half_ok) and co % 4 == 0) else "f32"))
+        half_out = dt == "f16"
         gdn_half = half_out and not use16 and gdn_half_ok
         if half_out and not use16 and not gdn_half:
             raise VcError("a half-precision output needs the fp16 path")
-        d = ConvDesc()
-        d.inp, d.out = x.view(True), (out.split_view() if sp_out else out.view(True))
-        d.wpk, d.bias = self.wpk.data_ptr(), self.bias.data_ptr()
         res_half = res is not None and res.dtype == "f16"
         if tail is not None and not (self.can_fuse_tail(tail) and use16 and half_in and epi == EPI_NONE and act < ACT_SIGMOID
                                      and chscale is None and not res_first):
             raise VcError("fused tail: a half-precision activation through a 3x3 C -> C layer of the fp16 path (PackedConv.can_fuse_tail)")
         if res_half and tail is None and not (use16 and self.half_res_ok and epi == EPI_NONE and act < ACT_SIGMOID):
             raise VcError("a half-precision residual needs the fp16 path's streaming 1x1 kernel (PackedConv.half_res_ok)")
+        flags = first | (CFG_OUT_SP3 if dt == "sp3" else 0)
+        if use16:
+            flags |= CFG_F16 | (CFG_IN_F16 if half_in else 0) | (CFG_OUT_F16 if half_out else 0) | (CFG_RES_F16 if res_half else 0)
+        # (the tuned choice is per shape AND per epilogue class: the streaming 1x1 kernel, for one, takes plain / ReLU / GDN epilogues but
+        #  not sigmoid or clamp, so a layer called both ways must not share one entry.  Not in the key: CFG_PACK128, stated on every call of
+        #  a layer packed with the 128-channel configuration -- the LDS-DMA kernel's blocks of 128 may run into the padding of 96 / 160 ...)
+        key = (x.n, x.h, x.w, flags) if (act < ACT_SIGMOID and epi == EPI_NONE) else (x.n, x.h, x.w, flags, act, epi)
+        if gdn_half:                  # the fp32 GDN instance of the streaming kernel, half store
+            return Route(False, dt, flags | CFG_OUT_F16, CFG_PWS | CFG_EXACT | flags | CFG_OUT_F16, None)
+        if tail is not None:          # out = tail(act(conv3x3(x))) + res in ONE launch of the LDS-DMA kernel
+            return Route(False, dt, flags, CFG_DMA | CFG_EXACT | flags | self._pack128, None)
+        # a half-precision residual: the streaming 1x1 kernel / the LDS-DMA 3x3 kernel (unless ``tuned`` pins the shape)
+        forced = ((CFG_PWS if self.k == 1 else CFG_DMA) | CFG_EXACT | flags | self._pack128) if flags & CFG_RES_F16 else None
+        return Route(False, dt, flags, forced, key)
+
+    def _describe(self, r, x, out, act, slope, res, epi, mul, in_xform, chscale, tail):
+        """The descriptor of a routed call, all but its configuration word (split windows: image distances in bytes)."""
+        d = ConvDesc()
+        d.inp = x.split_view() if x.dtype == "sp3" else x.view(True)
+        d.out = out.split_view() if out.dtype == "sp3" else out.view(True)
+        wpk, bias = self.split_pack() if r.split else (self.wpk16 if r.flags & CFG_F16 else self.wpk, self.bias)
+        d.wpk, d.bias = wpk.data_ptr(), bias.data_ptr()
         if res is not None:
-            d.res, d.res_sn, d.res_sh, d.res_sw = res.ptr, res.sn, res.sh, res.sw
+            d.res, d.res_sn, d.res_sh, d.res_sw = (res.ptr, res.image_bytes, 0, 0) if r.flags & CFG_RES_SP3 else (res.ptr, res.sn, res.sh, res.sw)
         if mul is not None:
             d.mul, d.mul_sn, d.mul_sh, d.mul_sw = mul.ptr, mul.sn, mul.sh, mul.sw
         if chscale is not None:
             d.chscale = chscale.data_ptr()
-        d.kh = d.kw = self.k
-        d.stride = self.stride
-        d.act, d.slope = act, slope
-        d.epi, d.in_xform = epi, in_xform
-        d.out_mode = OUT_PIXELSHUFFLE2 if self.ps else OUT_PLAIN
-        d.cfg = self.cfg
-        flags = (CFG_RES_FIRST if res_first else 0) | (CFG_OUT_SP3 if sp_out else 0)      # RES_FIRST: out = act(conv + res) instead of act(conv) + res
-        if use16:
-            d.wpk = self.wpk16.data_ptr()
-            flags |= CFG_F16 | (CFG_IN_F16 if half_in else 0) | (CFG_OUT_F16 if half_out else 0) | (CFG_RES_F16 if res_half else 0)
-        # (the tuned choice is per shape AND per epilogue class: the streaming 1x1 kernel, for one, takes plain / ReLU /
-        #  GDN epilogues but not sigmoid or clamp, so a layer called both ways must not share one entry)
-        key = (x.n, x.h, x.w, flags) if (act < ACT_SIGMOID and epi == EPI_NONE) else (x.n, x.h, x.w, flags, act, epi)
-        # (stated on every call of a layer packed with the 128-channel configuration; only the LDS-DMA kernel reads it: its
-        #  blocks of 128 may run into the padding of 96 / 160 / 432 ... output channels.  Not part of the tuning key.)
-        pack = CFG_PACK128 if self.cfg == 0 else 0
-        if gdn_half:                  # the fp32 GDN instance of the streaming kernel, half store
-            flags |= CFG_OUT_F16
-            d.cfg = CFG_PWS | CFG_EXACT | flags
-        elif tail is not None:        # out = tail(act(conv3x3(x))) + res in ONE launch of the LDS-DMA kernel
-            tw, tb = tail.tail_pack()
-            d.tail_wpk, d.tail_bias = tw.data_ptr(), tb.data_ptr()
-            d.cfg = CFG_DMA | CFG_EXACT | flags | pack
-        else:
-            d.cfg = self._pick_cfg(d, key, flags | pack) | pack
-        what = f"vc_conv2d_nhwc(k={self.k},s={self.stride},{self.cin}->{self.cout}{'+1x1 tail' if tail is not None else ''})"
+        if tail is not None:
+            d.tail_wpk, d.tail_bias = (t.data_ptr() for t in tail.tail_pack())
+        d.kh, d.kw, d.stride, d.out_mode = self.k, self.k, self.stride, (OUT_PIXELSHUFFLE2 if self.ps else OUT_PLAIN)
+        d.act, d.slope, d.epi, d.in_xform = act, slope, epi, in_xform
+        return d
+
+    def _launch(self, d, r, x, out, res, mul, tail):
+        """Launch a described call (and, while a KernelTimer collects, account for it under the layer's profiler key)."""
+        ho, wo, co = self.out_shape(x.h, x.w)
+        what = (f"vc_conv2d_nhwc(split k={self.k},{self.cin}->{self.cout})" if r.split else
+                f"vc_conv2d_nhwc(k={self.k},s={self.stride},{self.cin}->{self.cout}{'+1x1 tail' if tail is not None else ''})")
 
         def launch_once():
             # A tuned choice is keyed by shape and flags, not by the alignment class of the views: a later call of the same shape
             # on a sliced / unaligned view may be refused by a configuration that needs 16-byte accesses (LDS-DMA, streaming 1x1).
             # The general configuration of this packing takes any view: retry on it instead of failing the layer.
             rc = lib().vc_conv2d_nhwc(stream(), ctypes.byref(d))
-            if rc == -1 and tail is None and (d.cfg & 0xff) != self.cfg:
+            if rc == -1 and tail is None and not r.split and (d.cfg & 0xff) != self.cfg:
                 d.cfg = self.cfg | (d.cfg & ~0x1ff)
                 rc = lib().vc_conv2d_nhwc(stream(), ctypes.byref(d))
             return rc
         if timer is None:
-            check(launch_once(), what)
+            return check(launch_once(), what)
+        hq, wq = (ho // 2, wo // 2) if self.ps else (ho, wo)
+        flops = 2.0 * x.n * hq * wq * self.cout * (self.cin * self.k * self.k + (tail.cin if tail is not None else 0))
+        key = f"conv k{self.k}{'+k1' if tail is not None else ''} s{self.stride} {self.cin}->{self.cout} @{x.n}x{x.h}x{x.w}"
+        # bytes per element as stored: split tensors 6 (a classic layer's split store is counted as the fp32 values it holds), half 2
+        b_in, b_w = (6, 6) if r.split else (2 if r.flags & CFG_IN_F16 else 4, 2 if r.flags & CFG_F16 else 4)
+        b_out = 6 if r.split and r.flags & CFG_OUT_SP3 else (2 if r.flags & CFG_OUT_F16 else 4)
+        b_res = 6 if r.flags & CFG_RES_SP3 else (2 if r.flags & CFG_RES_F16 else 4)
+        nbytes = (x.n * x.h * x.w * self.cin * b_in + x.n * ho * wo * co * b_out + self.cout * self.cin * self.k * self.k * b_w
+                  + (x.n * ho * wo * co * b_res if res is not None else 0) + (x.n * ho * wo * co * 4 if mul is not None else 0))
+        if r.split:
+            g = self._split
+            split_keys.add(key)
+            kernel_symbols[key] = (f"conv_split_period_kernel<SplitPeriodCfg<{self.k}, {g.ntw}, {g.th}," if g.period else
+                                   f"conv_split_kernel<SplitCfg<{self.k}, {g.ntw}, {g.cpl}, {g.th},")
         else:
-            hq, wq = (ho // 2, wo // 2) if self.ps else (ho, wo)
-            flops = 2.0 * x.n * hq * wq * self.cout * (self.cin * self.k * self.k + (tail.cin if tail is not None else 0))
-            key = f"conv k{self.k}{'+k1' if tail is not None else ''} s{self.stride} {self.cin}->{self.cout} @{x.n}x{x.h}x{x.w}"
-            nbytes = (x.n * x.h * x.w * self.cin * (2 if half_in else 4) + x.n * ho * wo * co * (2 if half_out else 4)
-                      + self.cout * self.cin * self.k * self.k * (2 if use16 else 4)
-                      + (x.n * ho * wo * co * (2 if res_half else 4) if res is not None else 0) + (x.n * ho * wo * co * 4 if mul is not None else 0))
-            c0 = d.cfg & 0xff
-            if c0 == CFG_DMA:
-                kernel_symbols[key] = f"conv_dma_kernel<DmaCfg<{self.k}, {self.k}, {self.cin // (32 if use16 else 16)},"
-            elif c0 == CFG_PWS:
-                kernel_symbols[key] = "conv_pws_kernel<"
-            elif c0 == 7:
-                kernel_symbols[key] = f"conv_mfma_kernel<{self.k}, {self.k}, 1, 16, TileCfg<32, 16"
-            else:
-                kernel_symbols[key] = f"conv_mfma_kernel<{self.k}, {self.k}, {self.stride},"
-            timer.bracket(key, flops, lambda: check(launch_once(), what), nbytes)
+            kernel_symbols[key] = {CFG_DMA: f"conv_dma_kernel<DmaCfg<{self.k}, {self.k}, {self.cin // (32 if r.flags & CFG_F16 else 16)},",
+                                   CFG_PWS: "conv_pws_kernel<", CFG_N32T16: f"conv_mfma_kernel<{self.k}, {self.k}, 1, 16, TileCfg<32, 16",
+                                   }.get(d.cfg & 0xff, f"conv_mfma_kernel<{self.k}, {self.k}, {self.stride},")
+        timer.bracket(key, flops, lambda: check(launch_once(), what), nbytes)
+
+    def __call__(self, x, out=None, act=ACT_NONE, slope=0.01, res=None, epi=EPI_NONE, mul=None,
+                 in_xform=IN_NONE, chscale=None, out_f16=False, res_first=False, tail=None, out_sp3=False):
+        """``out_f16``: a hint that every consumer of the result is an fp16-path convolution (``half_ok``), so the result may be stored
+        as half (bit-identical downstream, half the traffic).  Honoured only when this layer itself runs on the fp16 path and allocates
+        its own output; otherwise the result stays fp32.  ``out_sp3``: the same for a consumer on the split-operand pipeline."""
+        r = self._route(x, out, act, slope, res, epi, mul, in_xform, chscale, out_f16, res_first, tail, out_sp3)
+        if r.split and x.dtype != "sp3":
+            x = split3(x, c_out=self.cin_split)
+        if out is None:
+            out = T.empty(x.n, *self.out_shape(x.h, x.w), x.buf.device, r.out_dtype)
+        d = self._describe(r, x, out, act, slope, res, epi, mul, in_xform, chscale, tail)
+        d.cfg = r.cfg if r.key is None else self._pick_cfg(d, r) | self._pack128
+        self._launch(d, r, x, out, res, mul, tail)
         return out
 
 

@@ -309,11 +309,15 @@ def run_sequential(seq, x, cache, final_chscale=None, final_act=None, out=None):
                 return None
         return packed[key]
 
+    def _is_block(m):
+        """a member with a ``run`` of its own (not a convolution this function packs)"""
+        return isinstance(m, (ResidualBlock, ResidualBlockWithStride, ResidualBlockUpsample, GDN)) or getattr(m, "vc_block", False)
+
     def takes_half(m):
         """May the member's input live in HBM as half (fp16 path)?"""
         if hasattr(m, "half_stream_ok"):
             return m.half_stream_ok()
-        if isinstance(m, (ResidualBlock, ResidualBlockWithStride, ResidualBlockUpsample, GDN)) or getattr(m, "vc_block", False):
+        if _is_block(m):
             return False
         pk = pack_of(m)
         return pk is not None and pk.half_ok
@@ -322,7 +326,7 @@ def run_sequential(seq, x, cache, final_chscale=None, final_act=None, out=None):
         """fp32 mode "split": may the member's input arrive as a split tensor (three bf16 pieces per value)?"""
         if hasattr(m, "split_in_ok"):
             return m.split_in_ok(n, h, w)
-        if isinstance(m, (ResidualBlockWithStride, GDN)) or getattr(m, "vc_block", False):
+        if _is_block(m):
             return False
         pk = pack_of(m)
         return pk is not None and hip.wants_split_at(pk, n, h, w)
@@ -331,7 +335,7 @@ def run_sequential(seq, x, cache, final_chscale=None, final_act=None, out=None):
     while i < len(mods):
         m = mods[i]
         last = i == len(mods) - 1
-        if isinstance(m, (ResidualBlock, ResidualBlockWithStride, ResidualBlockUpsample, GDN)) or getattr(m, "vc_block", False):
+        if _is_block(m):
             if last and (final_chscale is not None or final_act is not None):
                 raise hip.VcError("a block cannot take the sequence's final gain/activation")
             if last and out is not None:
@@ -564,14 +568,18 @@ class MeanScaleHyperprior(_Prepared):
         self.entropy_bottleneck = EntropyBottleneck(N)
         self.gaussian_conditional = GaussianConditional(None)
         self.N, self.M = int(N), int(M)
-        self._cache = {"g_a": {}, "h_a": {}, "h_s": {}, "g_s": {}}
+        self._cache = self._fresh_cache()
+
+    @staticmethod
+    def _fresh_cache():        # per transform: the packed weights run_sequential keeps
+        return {"g_a": {}, "h_a": {}, "h_s": {}, "g_s": {}}
 
     def _load_from_state_dict(self, *args, **kwargs):
-        self._cache = {"g_a": {}, "h_a": {}, "h_s": {}, "g_s": {}}
+        self._cache = self._fresh_cache()
         return super()._load_from_state_dict(*args, **kwargs)
 
     def _apply(self, fn, *a, **k):
-        self._cache = {"g_a": {}, "h_a": {}, "h_s": {}, "g_s": {}}
+        self._cache = self._fresh_cache()
         return super()._apply(fn, *a, **k)
 
     # -- checkpoint behaviour of CompressAI ------------------------------------------------------
@@ -856,27 +864,13 @@ class MeanScaleHyperprior(_Prepared):
         on another platform (the stream is then undecodable there).  The parity tests use it to show that such boundary
         cases are the ONLY thing between this decoder and a stream written by the reference on a CPU."""
         assert isinstance(strings, list) and len(strings) == 2
-        g, ig, hg, hig = gains
-        L = hip.lib()
         n = len(strings[1])
-        hz, wz = int(shape[0]), int(shape[1])
-        c = self.N
         eb_cdf, eb_len, eb_off = self.entropy_bottleneck.tables()
         gc_cdf, gc_len, gc_off = self.gaussian_conditional.tables()
-        z_index = np.repeat(np.arange(c, dtype=np.int32), hz * wz)
+        z_index = np.repeat(np.arange(self.N, dtype=np.int32), int(shape[0]) * int(shape[1]))
         z_sym = np.stack([hip.rans_decode(strings[1][i], z_index, eb_cdf, eb_len, eb_off) for i in range(n)])
-        z_sym_d = torch.from_numpy(z_sym).to(device)
-        z_hat = T.empty(n, hz, wz, c, device)
-        hip.check(L.vc_eb_dequant(hip.stream(), z_sym_d.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
-                                  None if hig is None else hig.data_ptr(), z_hat.view()), "vc_eb_dequant")
-        gp, _ = self._hs_for_bitstream(z_hat)
-        m = self.M
-        scales, means = gp.channels(0, m), gp.channels(m, 2 * m)
-        idx_d = torch.empty(n * m * gp.h * gp.w, dtype=torch.int32, device=device)
-        table = self._scale_table_dev()
-        hip.check(L.vc_gc_indexes(hip.stream(), scales.view(), table.data_ptr(), table.numel(), idx_d.data_ptr()),
-                  "vc_gc_indexes")
-        idx_h = idx_d.cpu().numpy().reshape(n, -1)
+        means, idx_d = self.hyper_decode_t(torch.from_numpy(z_sym).to(device), n, shape, gains)
+        idx_h = idx_d.cpu().numpy()
         if trace is not None:
             trace.update({"z_sym": z_sym, "y_idx": idx_h})
             if trace.get("y_idx_override") is not None:
@@ -884,8 +878,4 @@ class MeanScaleHyperprior(_Prepared):
         y_sym = np.stack([hip.rans_decode(strings[0][i], idx_h[i], gc_cdf, gc_len, gc_off) for i in range(n)])
         if trace is not None:
             trace["y_sym"] = y_sym
-        y_sym_d = torch.from_numpy(y_sym).to(device)
-        y_hat = T.empty(n, gp.h, gp.w, m, device)
-        hip.check(L.vc_gc_dequant(hip.stream(), y_sym_d.data_ptr(), means.view(), None if ig is None else ig.data_ptr(),
-                                  y_hat.view()), "vc_gc_dequant")
-        return run_sequential(self.g_s, y_hat, self._cache["g_s"], final_act=final_act)
+        return self.synth_decode_t(torch.from_numpy(y_sym).to(device), means, gains, final_act=final_act)
