@@ -354,6 +354,23 @@ int vc_gc_indexes(vc_stream s, vc_view scales, const float *scale_table, int n_s
 int vc_refine_scales(vc_stream s, vc_view scales, vc_view in, const float *w_oihw, const float *bias, const float *scale_table,
                      int n_scales, float rel_eps, int *counter);
 int vc_gc_dequant(vc_stream s, const int32_t *symbols, vc_view means, const float *out_gain, vc_view y_hat);
+/* Checkerboard passes of the ICIP2024 B-frame bitstream (additive to ABI 6: no struct changes).  Each call works on ONE parity of
+ * its views -- the positions with ((iy + ix) & 1) == parity; parity 1 = the anchors, as vc_quantize_mask's keep_parity -- and
+ * leaves every other position of y_hat untouched.  "Squeezed order": dense int32 [n][c][h][w/2], element (n,c,iy,ix) of the
+ * selected parity at column ix >> 1 (ckbd_anchor_sequeeze / ckbd_nonanchor_sequeeze, ICIP2024/src/model/elic.py:498-512).  w must
+ * be even and parity 0 or 1 (VC_EINVAL); h may be odd; all views of one call have one shape.
+ *   vc_gc_forward_ckbd: q = round(y*in_gain - mu); y_hat = (q + mu) * out_gain (y_hat.p nullable); symbols_sq = q and
+ *     indexes_sq = build_indexes(max(scales, 0.11)) in squeezed order (both required, with scale_table); bits_partial
+ *     (nullable; bits_slots = vc_bits_slots()) receives the -log2 p partial sums of the selected positions alone, p as in
+ *     vc_gc_forward.  in_gain / out_gain nullable.
+ *   vc_gc_indexes_ckbd: the decoder's indexes of one parity, squeezed order.
+ *   vc_gc_dequant_ckbd: y_hat = (symbols_sq + mu) * out_gain at the selected parity.
+ * Deterministic (no atomics). */
+int vc_gc_forward_ckbd(vc_stream s, vc_view y, vc_view scales, vc_view means, const float *in_gain, const float *out_gain,
+                       vc_view y_hat, int parity, double *bits_partial, int bits_slots, int32_t *symbols_sq,
+                       int32_t *indexes_sq, const float *scale_table, int n_scales);
+int vc_gc_indexes_ckbd(vc_stream s, vc_view scales, int parity, const float *scale_table, int n_scales, int32_t *indexes_sq);
+int vc_gc_dequant_ckbd(vc_stream s, const int32_t *symbols_sq, vc_view means, const float *out_gain, int parity, vc_view y_hat);
 /* Symbol refinement (ABI 6): the twin of vc_refine_scales for the coded integers.  `vc_refine_layer` names a convolution
  * (k x k, k odd <= 7, stride 1 or 2, padding k / 2, nn.Conv2d weights [cout][cin][k][k] as stored in the checkpoint, nullable
  * bias) whose output channels c0 .. c0 + C - 1 are the tensor under refinement, and `in` its channels-last fp32 input.

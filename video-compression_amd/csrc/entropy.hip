@@ -10,6 +10,7 @@
 // vc_bits_reduce folds the partials.  Symbols/indexes are written in the (n,c,y,x) order the range
 // coder consumes (CompressAI flattens NCHW tensors).
 #include "common.h"
+#include "ew_rowmap.h"
 
 #define ENT_BLOCK 256
 #define ENT_SLOTS 1024
@@ -237,6 +238,144 @@ extern "C" int vc_gc_dequant(vc_stream s, const int32_t *symbols, vc_view means,
     if (!symbols || !means.p || !y_hat.p) return VC_EINVAL;
     const long long total = (long long)y_hat.n * y_hat.h * y_hat.w * y_hat.c;
     hipLaunchKernelGGL(k_gc_dequant, dim3(ew_grid(total, ENT_BLOCK)), dim3(ENT_BLOCK), 0, as_stream(s), symbols, means, out_gain, y_hat);
+    VC_LAUNCH_CHECK();
+    return VC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Checkerboard passes of the ICIP2024 B-frame bitstream (vcamd/icip2024.py: _Elic.compress_t / decompress_t).  One launch works on
+// ONE parity of a channel group -- the positions with ((iy + ix) & 1) == parity, parity 1 = the anchors (vc_quantize_mask's
+// keep_parity) -- and exchanges integers with the host in the format's squeezed order: dense int32 [n][c][h][w/2], element
+// (n,c,iy,ix) at column ix >> 1 (ckbd_anchor_sequeeze / ckbd_nonanchor_sequeeze of ICIP2024/src/model/elic.py:498-512).  y_hat is
+// written at the selected positions only: the two passes of a group fill one tensor, no mask or merge launch in between.
+// Row-mapped like ew_kernels.hip (item = (ix >> 1, c) of a row, c fastest across lanes); the bit count keeps k_gc_forward's
+// scheme -- thread sums in double, fixed-order workgroup sum, one double per workgroup -- on at most ENT_SLOTS workgroups, and the
+// slots no workgroup owns are written as zero: vc_bits_reduce folds a whole row of ENT_SLOTS.  No atomics.
+// ------------------------------------------------------------------------------------------------
+static_assert(ENT_BLOCK == EW_BLOCK, "the row map counts its workgroups in EW_BLOCK threads");
+
+// row grid of a pass over n x h rows of `wh` half-columns x c channels with at most ENT_SLOTS workgroups; false: take the linear form
+static bool ckbd_row_grid(vc_rowmap &m, dim3 &grid, int n, int h, int wh, int c)
+{
+    if (!vc_rowmap_make(m, n, h, wh, c)) return false;
+    const long long bx = (m.items + ENT_BLOCK - 1) / ENT_BLOCK;
+    if (bx * n > ENT_SLOTS) return false;
+    long long gy = ENT_SLOTS / (bx * n);
+    if (gy > h) gy = h;
+    grid = dim3((unsigned)bx, (unsigned)gy, (unsigned)n);
+    return true;
+}
+
+static int ckbd_lin_grid(int n, int h, int wh, int c)
+{
+    const int g = ew_grid((long long)n * h * wh * c, ENT_BLOCK);
+    return g > ENT_SLOTS ? ENT_SLOTS : g;
+}
+
+#define VC_CKBD_LAUNCH(st, KERN, N, H, WH, C, ...)                                                                         \
+    do {                                                                                                                   \
+        vc_rowmap m_;                                                                                                      \
+        dim3 g_;                                                                                                           \
+        if (ckbd_row_grid(m_, g_, (N), (H), (WH), (C)))                                                                    \
+            KERN<true><<<g_, dim3(ENT_BLOCK), 0, (st)>>>(__VA_ARGS__, m_);                                                 \
+        else                                                                                                               \
+            KERN<false><<<dim3(ckbd_lin_grid((N), (H), (WH), (C))), dim3(ENT_BLOCK), 0, (st)>>>(__VA_ARGS__, vc_rowmap{0, 0, 0}); \
+    } while (0)
+
+static bool ckbd_shape_ok(const vc_view &v) { return v.p && v.n >= 1 && v.h >= 1 && v.w >= 2 && !(v.w & 1) && v.c >= 1; }
+static bool ckbd_same(const vc_view &a, const vc_view &b) { return a.n == b.n && a.h == b.h && a.w == b.w && a.c == b.c; }
+
+template <bool ROWS>
+__global__ void __launch_bounds__(ENT_BLOCK) k_gc_forward_ckbd(vc_view yv, vc_view sc, vc_view mu, const float *__restrict__ in_gain,
+                                                               const float *__restrict__ out_gain, vc_view yh, int parity,
+                                                               double *__restrict__ partial, int32_t *__restrict__ symbols,
+                                                               int32_t *__restrict__ indexes, const float *__restrict__ table,
+                                                               int n_scales, vc_rowmap m)
+{
+    __shared__ double sm[ENT_BLOCK / 64];
+    double bits = 0.0;
+    const float kc = -0.70710678118654752440f;  // float(-(2 ** -0.5))
+    const int wh = yv.w >> 1;
+    ew_for_each<ROWS>(m, yv.n, yv.h, wh, yv.c, [&](int n, int y, int xh, int c) {
+        const int x = 2 * xh + ((y ^ parity) & 1);
+        float v = yv.p[view_off(yv, n, y, x) + c];
+        if (in_gain) v *= in_gain[c];
+        const float mv = mu.p[view_off(mu, n, y, x) + c];
+        float s = sc.p[view_off(sc, n, y, x) + c];
+        s = fmaxf(s, 0.11f);                          // lower_bound_scale
+        const float q = rintf(v - mv);
+        const float yq = q + mv;
+        if (partial) {                                // the likelihood of k_gc_forward, term by term
+            const float a = fabsf(yq - mv);
+            const float upper = 0.5f * erfcf(kc * ((0.5f - a) / s));
+            const float lower = 0.5f * erfcf(kc * ((-0.5f - a) / s));
+            bits -= (double)log2f(fmaxf(upper - lower, 1e-9f));
+        }
+        if (yh.p) yh.p[view_off(yh, n, y, x) + c] = out_gain ? yq * out_gain[c] : yq;
+        const long long o = (((long long)n * yv.c + c) * yv.h + y) * wh + xh;
+        symbols[o] = (int32_t)q;
+        indexes[o] = scale_index(s, table, n_scales);
+    });
+    if (!partial) return;                             // (uniform over the grid)
+    const double r = block_sum(bits, sm);
+    if (threadIdx.x == 0) {
+        const unsigned nb = gridDim.x * gridDim.y * gridDim.z, b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        partial[b] = r;
+        for (unsigned k = b + nb; k < ENT_SLOTS; k += nb) partial[k] = 0.0;
+    }
+}
+
+extern "C" int vc_gc_forward_ckbd(vc_stream s, vc_view y, vc_view scales, vc_view means, const float *in_gain, const float *out_gain,
+                                  vc_view y_hat, int parity, double *bits_partial, int bits_slots, int32_t *symbols_sq,
+                                  int32_t *indexes_sq, const float *scale_table, int n_scales)
+{
+    if (!ckbd_shape_ok(y) || !scales.p || !means.p || !symbols_sq || !indexes_sq || !scale_table || n_scales < 2) return VC_EINVAL;
+    if (parity != 0 && parity != 1) return VC_EINVAL;
+    if (!ckbd_same(scales, y) || !ckbd_same(means, y) || (y_hat.p && !ckbd_same(y_hat, y))) return VC_EINVAL;
+    if (bits_partial && bits_slots != ENT_SLOTS) return VC_EINVAL;
+    VC_CKBD_LAUNCH(as_stream(s), k_gc_forward_ckbd, y.n, y.h, y.w >> 1, y.c, y, scales, means, in_gain, out_gain, y_hat, parity,
+                   bits_partial, symbols_sq, indexes_sq, scale_table, n_scales);
+    VC_LAUNCH_CHECK();
+    return VC_OK;
+}
+
+template <bool ROWS>
+__global__ void __launch_bounds__(ENT_BLOCK) k_gc_indexes_ckbd(vc_view sc, int parity, const float *__restrict__ table, int n_scales,
+                                                               int32_t *__restrict__ indexes, vc_rowmap m)
+{
+    const int wh = sc.w >> 1;
+    ew_for_each<ROWS>(m, sc.n, sc.h, wh, sc.c, [&](int n, int y, int xh, int c) {
+        const int x = 2 * xh + ((y ^ parity) & 1);
+        const float s = fmaxf(sc.p[view_off(sc, n, y, x) + c], 0.11f);
+        indexes[(((long long)n * sc.c + c) * sc.h + y) * wh + xh] = scale_index(s, table, n_scales);
+    });
+}
+
+extern "C" int vc_gc_indexes_ckbd(vc_stream s, vc_view scales, int parity, const float *scale_table, int n_scales, int32_t *indexes_sq)
+{
+    if (!ckbd_shape_ok(scales) || !scale_table || !indexes_sq || n_scales < 2 || (parity != 0 && parity != 1)) return VC_EINVAL;
+    VC_CKBD_LAUNCH(as_stream(s), k_gc_indexes_ckbd, scales.n, scales.h, scales.w >> 1, scales.c, scales, parity, scale_table, n_scales,
+                   indexes_sq);
+    VC_LAUNCH_CHECK();
+    return VC_OK;
+}
+
+template <bool ROWS>
+__global__ void __launch_bounds__(ENT_BLOCK) k_gc_dequant_ckbd(const int32_t *__restrict__ symbols, vc_view mu,
+                                                               const float *__restrict__ out_gain, int parity, vc_view yh, vc_rowmap m)
+{
+    const int wh = yh.w >> 1;
+    ew_for_each<ROWS>(m, yh.n, yh.h, wh, yh.c, [&](int n, int y, int xh, int c) {
+        const int x = 2 * xh + ((y ^ parity) & 1);
+        const float v = (float)symbols[(((long long)n * yh.c + c) * yh.h + y) * wh + xh] + mu.p[view_off(mu, n, y, x) + c];
+        yh.p[view_off(yh, n, y, x) + c] = out_gain ? v * out_gain[c] : v;
+    });
+}
+
+extern "C" int vc_gc_dequant_ckbd(vc_stream s, const int32_t *symbols_sq, vc_view means, const float *out_gain, int parity, vc_view y_hat)
+{
+    if (!symbols_sq || !means.p || !ckbd_shape_ok(y_hat) || !ckbd_same(means, y_hat) || (parity != 0 && parity != 1)) return VC_EINVAL;
+    VC_CKBD_LAUNCH(as_stream(s), k_gc_dequant_ckbd, y_hat.n, y_hat.h, y_hat.w >> 1, y_hat.c, symbols_sq, means, out_gain, parity, y_hat);
     VC_LAUNCH_CHECK();
     return VC_OK;
 }

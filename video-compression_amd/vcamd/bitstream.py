@@ -21,6 +21,7 @@ Flex-Rate is not offered here on purpose: its compress() codes the UN-gained lat
 one (quirk B.6), so the reference's own encoder and decoder disagree on the reconstruction whenever the gain differs from
 one -- there is no closed loop to pipeline.
 """
+import struct
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -199,3 +200,74 @@ class LhbdcStreamCodec:
 
     def close(self):
         self.pool.shutdown(wait=True)
+
+
+# ------------------------------------------------------------------------------------------------
+# ICIP2024 B-frame container (this project's own format: the reference has no bitstream for FlowGuidedB)
+# ------------------------------------------------------------------------------------------------
+# One byte string per coded frame, little-endian:
+#   offset  0  4 bytes  magic "VCIB"
+#           4  u8       version (1)
+#           5  u8       down_ratio (1, 2, 4, 8 or 16)
+#           6  u16 x 2  hyper-latent shape (h, w) = frame / 64
+#          10  f32 x 3  s (quality level), scale1, scale2 (both after FlowGuidedB.convert_scales)
+#          22  u32 x 12 string lengths: offset z, offset g0..g4, residual z, residual g0..g4
+#          70  the twelve payloads in that order
+ICIP2024_MAGIC = b"VCIB"
+ICIP2024_VERSION = 1
+ICIP2024_HEADER = struct.Struct("<4sBBHHfff")
+ICIP2024_LENGTHS = struct.Struct("<12I")
+ICIP2024_DOWN_RATIOS = (1, 2, 4, 8, 16)
+
+
+def _icip2024_payloads(strings, image):
+    out = []
+    for codec in ("offset", "residual"):
+        groups, z = strings[codec]
+        if len(groups) != 5:
+            raise hip.VcError(f"{codec}: five group strings per image, got {len(groups)}")
+        out.append(z[image])
+        out.extend(g[image] for g in groups)
+    return [bytes(b) for b in out]
+
+
+def pack_icip2024_frame(strings, shape, down_ratio, s, scale1, scale2, image=0):
+    """The container of image ``image`` of a FlowGuidedB.compress result: ``strings`` / ``shape`` / ``down_ratio`` as it returns
+    them, ``s`` the quality level and ``scale1`` / ``scale2`` the converted scales (FlowGuidedB.convert_scales) it was called
+    with.  The three numbers are stored as fp32 -- compress() and decompress() round the level to fp32 themselves and the
+    converted scales are fp32 values, so a decoder fed from the container uses the encoder's numbers."""
+    hz, wz = int(shape[0]), int(shape[1])
+    if int(down_ratio) not in ICIP2024_DOWN_RATIOS or not (1 <= hz <= 0xffff and 1 <= wz <= 0xffff):
+        raise hip.VcError(f"down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} do not fit the container")
+    payloads = _icip2024_payloads(strings, image)
+    if any(len(p) > 0xffffffff for p in payloads):
+        raise hip.VcError("a string is longer than the container's 32-bit length field")
+    head = ICIP2024_HEADER.pack(ICIP2024_MAGIC, ICIP2024_VERSION, int(down_ratio), hz, wz, float(s), float(scale1), float(scale2))
+    return head + ICIP2024_LENGTHS.pack(*(len(p) for p in payloads)) + b"".join(payloads)
+
+
+def unpack_icip2024_frame(data):
+    """Inverse of :func:`pack_icip2024_frame`: ``{"strings" (one image per list), "shape", "down_ratio", "s", "scale1", "scale2"}``.
+    Magic, version, field ranges and the total length are validated before anything is returned (VcError)."""
+    data = bytes(data)
+    fixed = ICIP2024_HEADER.size + ICIP2024_LENGTHS.size
+    if len(data) < fixed:
+        raise hip.VcError(f"ICIP2024 container: {len(data)} bytes is shorter than the {fixed}-byte header")
+    magic, version, down_ratio, hz, wz, s, scale1, scale2 = ICIP2024_HEADER.unpack_from(data, 0)
+    if magic != ICIP2024_MAGIC:
+        raise hip.VcError(f"ICIP2024 container: magic {magic!r} is not {ICIP2024_MAGIC!r}")
+    if version != ICIP2024_VERSION:
+        raise hip.VcError(f"ICIP2024 container: version {version} (this reader knows {ICIP2024_VERSION})")
+    if down_ratio not in ICIP2024_DOWN_RATIOS or hz < 1 or wz < 1:
+        raise hip.VcError(f"ICIP2024 container: down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} out of range")
+    if not all(np.isfinite(v) for v in (s, scale1, scale2)):
+        raise hip.VcError("ICIP2024 container: a header number is not finite")
+    lengths = ICIP2024_LENGTHS.unpack_from(data, ICIP2024_HEADER.size)
+    if fixed + sum(lengths) != len(data):
+        raise hip.VcError(f"ICIP2024 container: the length table asks for {fixed + sum(lengths)} bytes, the buffer has {len(data)}")
+    parts, pos = [], fixed
+    for n in lengths:
+        parts.append(data[pos:pos + n])
+        pos += n
+    strings = {"offset": [[[p] for p in parts[1:6]], [parts[0]]], "residual": [[[p] for p in parts[7:12]], [parts[6]]]}
+    return {"strings": strings, "shape": (hz, wz), "down_ratio": down_ratio, "s": s, "scale1": scale1, "scale2": scale2}

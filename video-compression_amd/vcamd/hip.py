@@ -180,6 +180,9 @@ def lib():
     sig("vc_gc_indexes", ci, vp, View, vp, ci, vp)
     sig("vc_refine_scales", ci, vp, View, View, vp, vp, vp, ci, cf, vp)
     sig("vc_gc_dequant", ci, vp, vp, View, vp, View)
+    sig("vc_gc_forward_ckbd", ci, vp, View, View, View, vp, vp, View, ci, vp, ci, vp, vp, vp, ci)
+    sig("vc_gc_indexes_ckbd", ci, vp, View, ci, vp, ci, vp)
+    sig("vc_gc_dequant_ckbd", ci, vp, vp, View, vp, ci, View)
     sig("vc_refine_y_symbols", ci, vp, View, RefineLayer, View, RefineLayer, cf, vp, View, vp, vp)
     sig("vc_refine_z_symbols", ci, vp, View, RefineLayer, vp, vp, cf, vp, View, vp, vp)
     sig("vc_bits_reduce", ci, vp, vp, ci, ci, vp)
@@ -207,7 +210,7 @@ EXPORTED_SYMBOLS = [
     "vc_spynet_preprocess", "vc_spynet_level_input", "vc_spynet_level_input_sp3", "vc_lhbdc_blend", "vc_flex_blend",
     "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar",
     "vc_attention_gate", "vc_sse_clamp01", "vc_select_flow", "vc_eb_forward", "vc_eb_dequant", "vc_gc_forward", "vc_gc_indexes", "vc_refine_scales",
-    "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
+    "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_gc_forward_ckbd", "vc_gc_indexes_ckbd", "vc_gc_dequant_ckbd", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
     # the operator spellings of SURVEY.md 8(b), thin forwards (csrc/abi_aliases.cpp)
     "vc_gdn", "vc_spynet_level", "vc_pool", "vc_upsample", "vc_pad", "vc_blend", "vc_factorized_bits", "vc_gaussian_symbols",

@@ -439,6 +439,169 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
             return t
         return hip.axpby(t, res, out=t)
 
+    # ---- real bitstream ------------------------------------------------------------------------------------------------------
+    # The reference only estimates this model's rate; the format below is this project's own and follows
+    # the intra codec's conventions (ELIC.compress / decompress): one string for the hyper-latents and ONE string per channel
+    # group, the anchor symbols (checkerboard positions with (row + col) odd, coded with the checkerboard-context slice at zero)
+    # followed by the non-anchor symbols (coded with the checkerboard context of the just-decoded anchors); per image of the
+    # batch its own strings.  Coded values: z symbols = round(z * hypergain - median), z_hat = (symbol + median) * invhypergain;
+    # y symbols = round(y * gain - mu), decoder-side latents round(y - mu) + mu in the gained domain (what the channel and
+    # checkerboard contexts read), synthesis and heads read them times invgain.  The integers cross to and from the host in the
+    # format's squeezed order only (vc_gc_forward_ckbd / vc_gc_indexes_ckbd / vc_gc_dequant_ckbd): the two passes of a group fill
+    # ONE y_hat tensor, no parity mask, merge or numpy re-ordering in between.
+    def _scale_table_dev(self):
+        gc = self.gaussian_conditional
+        if gc._packed is None:
+            if gc.scale_table.numel() == 0:
+                raise hip.VcError("scale table is empty: call update(force=True) after loading weights")
+            gc._packed = gc.scale_table.detach().float().contiguous().to(gc.scale_bound.device)
+        return gc._packed
+
+    def _hyper_buffers(self, z_hat, temporal_into):
+        """hyper = prior_fusion([h_s(z_hat) | temporal condition]) in the inputs of the entropy-parameter networks: (pin0, pin) =
+        [ctx | hyper] of group 0 and [ctx | channel ctx | hyper] of the others.  Encoder and decoder build them through this one
+        function: the same launches on the same layouts."""
+        M = self.M
+        dev, n, h, w = z_hat.buf.device, z_hat.n, 4 * z_hat.h, 4 * z_hat.w
+        fusion_in = T.empty(n, h, w, 2 * M, dev)                       # [h_s(z_hat) | temporal condition]
+        self.seq("h_s", z_hat, out=fusion_in.channels(0, M))
+        temporal_into(fusion_in.channels(M, 2 * M))
+        pin = T.empty(n, h, w, 6 * M, dev)
+        hyper = self.seq("prior_fusion", fusion_in, out=pin.channels(4 * M, 6 * M))
+        pin0 = T.empty(n, h, w, 4 * M, dev)
+        hip.axpby(hyper, None, out=pin0.channels(2 * M, 4 * M))
+        return pin0, pin
+
+    def _group_passes(self, pin0, pin, y_hat):
+        """The ten entropy-parameter passes of a frame, in coding order: yields (group, c0, c1, parity, scales, means) with the two
+        Gaussian-parameter views of the pass.  The caller fills ``y_hat`` (zero-initialised, gained domain) at the pass's parity of
+        channels c0:c1 before it asks for the next pass: the non-anchor pass and the later groups read it."""
+        M = self.M
+        bounds = GROUPS + (M,)
+        for i in range(5):
+            c0, c1 = bounds[i], bounds[i + 1]
+            cg = c1 - c0
+            p = pin0 if i == 0 else pin
+            hip.axpby(p.channels(p.c - 2 * M, p.c), None, alpha=0.0, out=p.channels(0, 2 * M))   # anchor pass: ctx = 0 (hyper is finite)
+            if i > 0:
+                self._sub("channel_context_models", i - 1, y_hat.channels(0, c0), out=p.channels(2 * M, 4 * M))
+            for parity in (1, 0):
+                if parity == 0:                    # the group's anchors are in y_hat, its non-anchors still zero
+                    self._ctx_conv(i)(y_hat.channels(c0, c1), out=p.channels(0, 2 * M))
+                gp = self._sub("entropy_parameters", i, p)
+                yield i, c0, c1, parity, gp.channels(0, cg), gp.channels(cg, 2 * cg)
+
+    def _synthesis_heads(self, y_hat, invgain, f1d, f2d, f3d, res):
+        y_syn = hip.channel_scale(y_hat, invgain)
+        xhat3 = self.seq("g_s3", y_syn)
+        head3 = self._head("g_o3", [xhat3, f3d], res[2])
+        xhat2 = self.seq_cat("g_s2", [xhat3, f3d])
+        head2 = self._head("g_o2", [xhat2, f2d], res[1])
+        xhat1 = self.seq_cat("g_s1", [xhat2, f2d])
+        head1 = self._head("g_o1", [xhat1, f1d], res[0])
+        return head1, head2, head3
+
+    def _trace_latents(self, trace, y_hat, z_hat):
+        bounds = GROUPS + (self.M,)
+        trace["y_hat"] = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
+        trace["z_hat"] = hip.nhwc_to_nchw(z_hat)
+
+    def compress_t(self, enc1, enc2, enc3, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None):
+        """Encoder of the bitstream path on channels-last views (arguments as :meth:`code`).  Returns ``{"strings": [[[g0 per
+        image], ..., [g4 per image]], [z per image]], "shape": (hz, wz), "heads": the three decoder heads computed from the y_hat
+        the decoder rebuilds (closed loop), "bits": 0-dim float64 device tensor, the -log2 p sum of exactly the coded symbols (the
+        z row + two parity rows per group)}``.  ``trace``: receives "y_hat" (five NCHW tensors, gained domain), "z_hat" and
+        "passes" (per pass a dict group / c0 / c1 / parity / y / scales / means of views)."""
+        L, M = hip.lib(), self.M
+        gain, hypergain, invhypergain, invgain = self.interpolate_gain(s)
+        y = self.seq_cat("g_a1", enc1) if len(enc1) > 1 else self.seq("g_a1", enc1[0])
+        y = self.seq_cat("g_a2", [y] + enc2)
+        y = self.seq_cat("g_a3", [y] + enc3)
+        dev, n, h, w = y.buf.device, y.n, y.h, y.w
+        y = hip.channel_scale(y, gain, out=y)
+        z = self.seq("h_a", y, final_chscale=hypergain)
+        if (h, w) != (4 * z.h, 4 * z.w) or w % 2:
+            raise hip.VcError(f"latent {h}x{w} / hyper-latent {z.h}x{z.w}: the frame must be a multiple of 64")
+        bits = BitCounter(dev, max_rows=11)
+        table = self._scale_table_dev()
+        z_hat = T.empty(n, z.h, z.w, z.c, dev)
+        z_sym = torch.empty((n, z.c * z.h * z.w), dtype=torch.int32, device=dev)
+        hip.check(L.vc_eb_forward(hip.stream(), z.view(), self.entropy_bottleneck.device_params().data_ptr(), None,
+                                  invhypergain.data_ptr(), z_hat.view(), z_sym.data_ptr(), bits.next_row_ptr(), bits.slots, None),
+                  "vc_eb_forward")
+        pin0, pin = self._hyper_buffers(z_hat, temporal_into)
+        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
+        coded = [[] for _ in range(5)]                                 # per group the (symbols, indexes) of its two passes
+        if trace is not None:
+            trace["passes"] = []
+        for i, c0, c1, parity, scales, means in self._group_passes(pin0, pin, y_hat):
+            sym = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
+            idx = torch.empty_like(sym)
+            hip.check(L.vc_gc_forward_ckbd(hip.stream(), y.channels(c0, c1).view(), scales.view(), means.view(), None, None,
+                                           y_hat.channels(c0, c1).view(), parity, bits.next_row_ptr(), bits.slots, sym.data_ptr(),
+                                           idx.data_ptr(), table.data_ptr(), table.numel()), "vc_gc_forward_ckbd")
+            coded[i].append((sym, idx))
+            if trace is not None:
+                trace["passes"].append({"group": i, "c0": c0, "c1": c1, "parity": parity, "y": y.channels(c0, c1), "scales": scales,
+                                        "means": means})
+        heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
+        total = bits.totals().sum()
+        # the only device -> host traffic of the pass: squeezed int32 tensors (one synchronisation, after the last launch)
+        eb_tables = self.entropy_bottleneck.tables()
+        gc_tables = self.gaussian_conditional.tables()
+        z_index = np.repeat(np.arange(z.c, dtype=np.int32), z.h * z.w)
+        z_strings = [hip.rans_encode(row, z_index, *eb_tables) for row in z_sym.cpu().numpy()]
+        strings = []
+        for passes in coded:
+            host = [(sym.cpu().numpy(), idx.cpu().numpy()) for sym, idx in passes]
+            strings.append([hip.rans_encode(np.concatenate([sy[j] for sy, _ in host]), np.concatenate([ix[j] for _, ix in host]),
+                                            *gc_tables) for j in range(n)])
+        if trace is not None:
+            self._trace_latents(trace, y_hat, z_hat)
+            trace["heads"] = heads
+        return {"strings": [strings, z_strings], "shape": (z.h, z.w), "heads": heads, "bits": total}
+
+    def decompress_t(self, strings, shape, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None):
+        """Decoder of :meth:`compress_t`: decoder-side inputs only.  Returns the three heads.  Two decode_stream calls per group
+        string on one RansStreamDecoder per image."""
+        L, M = hip.lib(), self.M
+        dev = self.Gain.device
+        _, _, invhypergain, invgain = self.interpolate_gain(s)
+        hz, wz = int(shape[0]), int(shape[1])
+        if len(strings) != 2 or len(strings[0]) != 5 or not strings[1] or any(len(g) != len(strings[1]) for g in strings[0]):
+            raise hip.VcError("strings: [[g0, ..., g4], z] with one byte string per image in each of the six lists")
+        if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
+            raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
+        n = len(strings[1])
+        h, w = 4 * hz, 4 * wz
+        table = self._scale_table_dev()
+        eb_tables = self.entropy_bottleneck.tables()
+        gc_tables = self.gaussian_conditional.tables()
+        z_index = np.repeat(np.arange(self.N, dtype=np.int32), hz * wz)
+        z_sym = torch.from_numpy(np.stack([hip.rans_decode(strings[1][j], z_index, *eb_tables) for j in range(n)])).to(dev)
+        z_hat = T.empty(n, hz, wz, self.N, dev)
+        hip.check(L.vc_eb_dequant(hip.stream(), z_sym.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
+                                  invhypergain.data_ptr(), z_hat.view()), "vc_eb_dequant")
+        pin0, pin = self._hyper_buffers(z_hat, temporal_into)
+        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
+        decoders, keep = None, []
+        for i, c0, c1, parity, scales, means in self._group_passes(pin0, pin, y_hat):
+            if parity == 1:
+                decoders = [hip.RansStreamDecoder(strings[0][i][j]) for j in range(n)]
+            idx = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
+            hip.check(L.vc_gc_indexes_ckbd(hip.stream(), scales.view(), parity, table.data_ptr(), table.numel(), idx.data_ptr()),
+                      "vc_gc_indexes_ckbd")
+            idx_host = idx.cpu().numpy()
+            sym = torch.from_numpy(np.stack([decoders[j].decode_stream(idx_host[j], *gc_tables) for j in range(n)])).to(dev)
+            keep.append(sym)                                           # (must outlive the launch that reads it)
+            hip.check(L.vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None, parity, y_hat.channels(c0, c1).view()),
+                      "vc_gc_dequant_ckbd")
+        heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
+        if trace is not None:
+            self._trace_latents(trace, y_hat, z_hat)
+            trace["heads"] = heads
+        return heads
+
 
 class Offset_ELIC(_Elic):
     def __init__(self, N=128, M=128, **kwargs):
@@ -753,6 +916,12 @@ def _f32_round2(v):
     return float((torch.round(t * 10 ** 2) / (10 ** 2)).item())
 
 
+def _flat_strings(codec_strings):
+    """[[[g0], ..., [g4]], [z]] -> every byte string of it"""
+    groups, z = codec_strings
+    return [b for g in groups for b in g] + list(z)
+
+
 class FlowGuidedB(nn.Module):
     def __init__(self):
         super().__init__()
@@ -879,6 +1048,114 @@ class FlowGuidedB(nn.Module):
         return {"x_hat": hip.nhwc_to_nchw(x_hat), "size": (size_offset + size_res).float(),
                 "rate": (size_offset / num_pixels + size_res / num_pixels).float(),
                 "size_offset": size_offset, "size_residual": size_res}
+
+    # -- real bitstream (this project's own format: the reference has none for this model) ----------------
+    SEARCH_RATIOS = (1, 2, 4, 8, 16)
+
+    def _bitstream_pass(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio, strings=None, shape=None, trace=None):
+        """The stages of :meth:`forward_device` with the two compressors on their bitstream paths; ``xcur`` is None on the decoder,
+        which runs the reference-only stages through the same launches on the same buffer layouts (the per-level buffers keep
+        their fcur slice, unused): every tensor the entropy path reads comes out of the same kernel instances on both sides."""
+        enc = xcur is not None
+        dev, n = xref1.buf.device, xref1.n
+        if xref1.h % 64 or xref1.w % 64 or (xref2.n, xref2.h, xref2.w) != (n, xref1.h, xref1.w):
+            raise hip.VcError("frame size must be a multiple of 64 (the reference pads with utils.pad), both references alike")
+        s1, s2 = self.convert_scales(scale1, scale2)
+        flow = self.estimate_flow_t(xref1, xref2, down_ratio)
+        chans = (64, 96, 128)
+        # per level one buffer [wref1 | wref2 | fref1 | fref2 | fcur], as forward_device lays it out
+        F_ = [T.empty(n, xref1.h >> (l + 1), xref1.w >> (l + 1), 5 * c, dev) for l, c in enumerate(chans)]
+        sl = lambda l, j: F_[l].channels(j * chans[l], (j + 1) * chans[l])  # noqa: E731
+        fref1 = self.feature_extractor.run(xref1, outs=[sl(l, 2) for l in range(3)])
+        fref2 = self.feature_extractor.run(xref2, outs=[sl(l, 3) for l in range(3)])
+        fcur = self.feature_extractor.run(xcur, outs=[sl(l, 4) for l in range(3)]) if enc else None
+        flows = []
+        for l in range(3):                                   # get_warpedrefs_at_layer (m.py:104-119)
+            fc1 = hip.axpby(flow.channels(0, 2), None, alpha=s1)
+            fc2 = hip.axpby(flow.channels(2, 4), None, alpha=s2)
+            flows.append((fc1, fc2))
+            hip.warp(hip.WARP_W3, fref1[l], fc1, out=sl(l, 0))
+            hip.warp(hip.WARP_W3, fref2[l], fc2, out=sl(l, 1))
+            if l < 2:
+                flow = hip.avgpool_reflectpad(flow, 2, scale=0.5)
+        cond = [F_[l].channels(0, 4 * chans[l]) for l in range(3)]
+        t_off, t_res = ({}, {}) if trace is not None else (None, None)
+        oc, rc = self.offset_compressor, self.residual_compressor
+        off_cond = lambda dst: self.offset_temporal_conditioner.run(cond[0], cond[1], cond[2], out=dst)  # noqa: E731
+        out = {}
+        if enc:
+            out["offset"] = oc.compress_t([F_[0]], [F_[1]], [F_[2]], cond[0], cond[1], cond[2], off_cond, s, trace=t_off)
+            offs = out["offset"]["heads"]
+        else:
+            offs = oc.decompress_t(strings["offset"], shape, cond[0], cond[1], cond[2], off_cond, s, trace=t_off)
+        comp = []
+        for l, (off, div) in enumerate(((offs[0], self.offset_diversity_l1), (offs[1], self.offset_diversity_l2),
+                                        (offs[2], self.offset_diversity_l3))):
+            hc = off.c // 2
+            comp.append(div.run(fref1[l], off.channels(0, hc), flows[l][0], fref2[l], off.channels(hc, 2 * hc), flows[l][1]))
+        res_cond = lambda dst: self.residue_temporal_conditioner.run(comp[0], comp[1], comp[2], out=dst)  # noqa: E731
+        if enc:
+            out["residual"] = rc.compress_t([fcur[0], comp[0]], [fcur[1], comp[1]], [fcur[2], comp[2]], comp[0], comp[1], comp[2],
+                                            res_cond, s, res=tuple(comp), trace=t_res)
+            xs = out["residual"]["heads"]
+        else:
+            xs = rc.decompress_t(strings["residual"], shape, comp[0], comp[1], comp[2], res_cond, s, res=tuple(comp), trace=t_res)
+        if trace is not None:
+            trace.update({"offset": t_off, "residual": t_res})
+        out["x_hat"] = self.reconstructor.run(*xs)
+        return out
+
+    @staticmethod
+    def _coding_level(s):
+        """the quality level as the container stores it (fp32): both sides interpolate the gains from the same number"""
+        return float(np.float32(s))
+
+    def compress(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio=None, trace=None):
+        """Encode a B-frame for real.  NCHW CUDA tensors and host numbers as :meth:`forward`; ``down_ratio=None`` searches the
+        flow resolution on the device (:meth:`search_flow_t`) and reads the choice to the host.  Returns ``{"strings": {"offset",
+        "residual"} each [[[g0], ..., [g4]], [z]] with one byte string per image in every inner list, "shape": hyper-latent
+        (h, w), "down_ratio", "x_hat": the reconstruction :meth:`decompress` rebuilds, "size": the real bit count (8 x string
+        bytes), "size_estimate": -log2 p of the coded symbols on the device}``.  The convolutions run on the pipeline of
+        hip.BITSTREAM_HS_MODE whatever VC_FP32_MODE says: both compressors' entropy parameters depend on every stage in front
+        of them, so the whole pass decides how the strings are read."""
+        _require_frames(xref1, xref2, xcur)
+        s = self._coding_level(s)
+        r1, r2, c = hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), hip.nchw_to_nhwc(xcur)
+        if down_ratio is None:                 # (the choice travels in the stream: the search itself needs no pinning)
+            _, choice, _ = self.search_flow_t(c, r1, r2, scale1, scale2, self.SEARCH_RATIOS)
+            picks = sorted({self.SEARCH_RATIOS[int(k)] for k in choice.cpu().tolist()})
+            if len(picks) != 1:
+                raise hip.VcError(f"the images of the batch choose different flow resolutions {picks}: encode them one by one")
+            down_ratio = picks[0]
+        down_ratio = int(down_ratio)
+        if down_ratio not in self.SEARCH_RATIOS:
+            raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
+        with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
+            out = self._bitstream_pass(r1, r2, scale1, scale2, c, s, down_ratio, trace=trace)
+            x_hat = hip.nhwc_to_nchw(out["x_hat"])
+        strings = {k: out[k]["strings"] for k in ("offset", "residual")}
+        nbytes = sum(len(b) for k in strings for b in _flat_strings(strings[k]))
+        estimate = float((out["offset"]["bits"] + out["residual"]["bits"]).item())
+        return {"strings": strings, "shape": out["offset"]["shape"], "down_ratio": down_ratio, "x_hat": x_hat, "size": 8 * nbytes,
+                "size_estimate": estimate}
+
+    def decompress(self, xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace=None):
+        """Decode the strings of :meth:`compress` from the two references alone: ``{"x_hat"}``."""
+        _require_frames(xref1, xref2)
+        s = self._coding_level(s)
+        down_ratio = int(down_ratio)
+        if down_ratio not in self.SEARCH_RATIOS:
+            raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
+        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"}:
+            raise hip.VcError('strings: {"offset": ..., "residual": ...}')
+        hz, wz = int(shape[0]), int(shape[1])
+        if (64 * hz, 64 * wz) != tuple(xref1.shape[2:]) or len(strings["offset"][1]) != xref1.shape[0]:
+            raise hip.VcError(f"hyper-latent shape {hz}x{wz} / {len(strings['offset'][1])} image(s) do not belong to references "
+                              f"{tuple(xref1.shape)}")
+        with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
+            out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), scale1, scale2, None, s, down_ratio,
+                                       strings=strings, shape=(hz, wz), trace=trace)
+            return {"x_hat": hip.nhwc_to_nchw(out["x_hat"])}
 
     # -- motion-adaptive flow resolution (opt_helpers.py:23-51) --------------------------------------------
     def _predict_from_flow(self, flow, xref1, xref2, s1, s2):
