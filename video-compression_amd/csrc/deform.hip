@@ -361,6 +361,24 @@ inline bool aligned16(const vc_view &v)
     return (reinterpret_cast<uintptr_t>(v.p) % 16 == 0) && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0;
 }
 
+// Largest LDS allocation of a workgroup on the current device in bytes, queried once per device (0: the query failed).
+inline size_t lds_limit()
+{
+    static std::atomic<int> cached[VC_MAX_DEVICES];
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= VC_MAX_DEVICES) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if ((v = cached[dev].load(std::memory_order_relaxed)) > 0) return (size_t)v;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    cached[dev].store(v, std::memory_order_relaxed);
+    return (size_t)v;
+}
+
 template <int CG, int OG, bool FUSED> int launch(hipStream_t st, const DeformArgs &a_in, bool vec)
 {
     DeformArgs a = a_in;
@@ -378,10 +396,15 @@ template <int CG, int OG, bool FUSED> int launch(hipStream_t st, const DeformArg
     };
     if (a.x_half && !(fits32(a.x1) && fits32(a.x2))) return VC_EINVAL;
     const size_t lds = (((vec && a.x_half) ? (size_t)0 : (size_t)half * 9 * CG * OG) + (FUSED ? 64 * (27 * half + 1) : 0)) * sizeof(float);
+    // more LDS than a workgroup of this device can have (fused, 32 groups of 16 -> 8 channels: 184 KB) is a shape this library does
+    // not serve: refused here, before any launch, like every other unsupported shape
+    if (lds > 64 * 1024 && lds > lds_limit()) return VC_EINVAL;
     auto launch_one = [&](auto kern) {
         if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError();                       // (consumed here: the next launch check of the library must not report it as its own)
             return VC_ELAUNCH;
+        }
         hipLaunchKernelGGL(kern, grid, block, lds, st, a);
         return hipGetLastError() == hipSuccess ? VC_OK : VC_ELAUNCH;
     };
@@ -408,8 +431,9 @@ template <int CG, int OG, bool FUSED> int launch(hipStream_t st, const DeformArg
 
 template <bool FUSED> int dispatch(hipStream_t st, const DeformArgs &a, int cg, int og)
 {
-    // (half features: a group's 2 * cg bytes start 8-byte aligned; a 16-byte gather that is only 8-byte aligned is legal)
-    auto aligned8h = [](const vc_view &v) { return (reinterpret_cast<uintptr_t>(v.p) % 16 == 0) && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0; };
+    // (half features: pointer and strides -- in halves -- whole 8-byte units.  That is all the gathers need: a group's 2 * cg bytes
+    //  start 8-byte aligned anyway (cg = 4, 12: every other group), and a 16-byte gather that is only 8-byte aligned is legal)
+    auto aligned8h = [](const vc_view &v) { return (reinterpret_cast<uintptr_t>(v.p) % 8 == 0) && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0; };
     const bool vec = a.x_half ? (cg % 4 == 0 && aligned8h(a.x1) && aligned8h(a.x2)) : (cg % 4 == 0 && aligned16(a.x1) && aligned16(a.x2));
     if (a.x_half && !FUSED) return VC_EINVAL;
     switch (cg * 16 + og) {
