@@ -443,6 +443,105 @@ int vc_rans_decode_stream(const uint8_t *data, size_t nbytes, uint64_t *state, c
                           const int32_t *offsets, int32_t *symbols_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Interleaved range coder (host reference + device kernels, csrc/rans_lanes.h / rans_device.hip).  The string format of
+ * the ICIP2024 B-frame codec's coder="device" path -- this project's own; additive
+ * to ABI 6: no existing struct changes.
+ *
+ * Arithmetic of the host coder above (64-bit state, lower bound 2^31, 32-bit words, 16-bit probabilities, value = symbol -
+ * offset, slot cdf_size - 2 = escape), run on 64 * W lanes in lockstep: symbol i of a SEGMENT belongs to global lane
+ * i % (64 W), round i / (64 W); wave w owns lanes 64 w .. 64 w + 63 and one sub-stream.  A PAYLOAD is the W sub-streams one
+ * after the other, each  u32 word count | 64 x u64 final states (lane order) | the words in the order the decoder reads
+ * them  -- W * 516 + 4 * words bytes.  Per round the active lanes decode one symbol; the lanes whose state fell below 2^31
+ * take the next words of their sub-stream in ascending lane order; an escaped value follows in the same lane as two
+ * 16-bit uniform steps (frequency 1: low half, then high half) of the zig-zag of (symbol - offset) taken modulo 2^32 (every
+ * int32 symbol has an encoding).  A payload codes a TABLE of segments one after the other, states and cursors continuing.
+ * W: a power of two in 1 .. 16.  Tables: every cdf strictly increasing from 0 to 65536 over cdf_size entries (VC_EINVAL
+ * otherwise) -- what vc_pmf_to_quantized_cdf produces.
+ * ---------------------------------------------------------------------------------------- */
+#define VC_IRANS_MAX_WAVES 16
+#define VC_IRANS_MAX_SEGMENTS 16       /* device encoder only */
+#define VC_IRANS_MAX_TABLE_SETS 4      /* device encoder only */
+#define VC_IRANS_SUBSTREAM_HEADER 516  /* bytes: u32 word count + 64 u64 states */
+typedef struct vc_irans_tables {       /* host: one table set, as the vc_rans_* entry points take it */
+    const int32_t *cdfs;
+    int n_tables, cdf_stride;
+    const int32_t *cdf_sizes, *offsets;
+} vc_irans_tables;
+typedef struct vc_irans_segment {      /* host: `count` symbols with one table index each, coded with table set `table_set` */
+    int32_t *symbols;                  /* encoder: read; decoder: written */
+    const int32_t *indexes;
+    size_t count;
+    int table_set;
+} vc_irans_segment;
+/* Capacity in bytes that holds the payload of ONE segment of `count` symbols whatever their values (a step emits at most
+ * one word, an escaped symbol takes three steps); a segment table needs at most the sum over its segments.  0 for a bad W.
+ * vc_irans_wave_words: the words of that capacity per wave, 192 * ceil(count / (64 W)). */
+size_t vc_irans_bound(size_t count, int waves);
+size_t vc_irans_wave_words(size_t count, int waves);
+/* returns the payload's bytes (>= 0) or a negative VC_E* code (VC_ENOMEM: out_cap too small) */
+long long vc_irans_encode_host(const vc_irans_segment *segs, int n_segs, const vc_irans_tables *sets, int n_sets, int waves,
+                               uint8_t *out, size_t out_cap);
+/* Validates W and the word counts against nbytes before anything is decoded, every word read against its sub-stream's end,
+ * every index against n_tables and the final cursors against the word counts: VC_EINVAL / VC_EDATA, never an out-of-bounds
+ * read. */
+int vc_irans_decode_host(const uint8_t *data, size_t nbytes, const vc_irans_segment *segs, int n_segs,
+                         const vc_irans_tables *sets, int n_sets, int waves);
+/* Device form of a table set: the used entries of every row back to back as u16 (65536 wraps to 0; never read as a start)
+ * and per table four int32 {first entry, cdf_size, offset, mode = the widest bin, where the symbol search starts}.  Returns
+ * the number of u16 entries (padded to a multiple of 8) or a negative code; both outputs nullable (size query / validation:
+ * pass NULLs, allocate, call again).  Host memory only. */
+long long vc_irans_pack_tables(const int32_t *cdfs, int n_tables, int cdf_stride, const int32_t *cdf_sizes, const int32_t *offsets,
+                               uint16_t *cdf16_out, int32_t *rows_out /* [n_tables][4] */);
+typedef struct vc_irans_dtables {      /* device copies of vc_irans_pack_tables' outputs */
+    const uint16_t *cdf16;             /* 16-byte aligned */
+    const int32_t *rows;
+    int n_tables, entries;
+} vc_irans_dtables;
+typedef struct vc_irans_dsegment {     /* device: dense [images][count] int32 tensors */
+    const int32_t *symbols, *indexes;
+    uint32_t count;                    /* per image */
+    int table_set;
+} vc_irans_dsegment;
+/* 1 when the decode kernel stages a table set of `entries` u16 in LDS, 0 when it reads it from global memory */
+int vc_irans_tables_in_lds(int entries);
+/* One launch codes the segment table of `images` images: grid = images x W, one wave per workgroup, rounds and segments
+ * walked backwards.  out: images * W regions of (129 + wave_cap_words) u32 each, wave_cap_words >= the sum of
+ * vc_irans_wave_words over the segments (VC_EINVAL otherwise); the region of (image, wave) ENDS with that wave's
+ * sub-stream (count | states | words).  counts [images * W] receives the word counts -- the sub-stream of a region starts
+ * wave_cap_words - count u32 into it -- or 0xffffffff where an index was out of range.  segs / sets: host arrays. */
+int vc_irans_encode(vc_stream s, const vc_irans_dsegment *segs, int n_segs, const vc_irans_dtables *sets, int n_sets, int images,
+                    int waves, uint32_t *out, size_t wave_cap_words, uint32_t *counts);
+/* Decoder state of one image between launches (device memory; the host reads it once, after the last launch). */
+#define VC_IRANS_ERR_HEADER 1u         /* W sub-stream headers / word counts do not fit the payload's length */
+#define VC_IRANS_ERR_WORD 2u           /* a word was asked for past its sub-stream's end */
+#define VC_IRANS_ERR_INDEX 4u          /* a table index >= n_tables */
+typedef struct vc_irans_dstate {
+    uint32_t error;                    /* sticky OR of VC_IRANS_ERR_* over the waves: what the host reads */
+    uint32_t waves;
+    uint32_t base[VC_IRANS_MAX_WAVES];    /* first word of the wave's sub-stream, in u32 from `payloads` */
+    uint32_t count[VC_IRANS_MAX_WAVES];   /* its word count */
+    uint32_t cursor[VC_IRANS_MAX_WAVES];  /* words consumed: must equal count after the last segment */
+    /* What the kernels themselves act on, so that the zeros behind a violation do not depend on timing: a wave that meets one
+     * in its launch number j (0, 1, ...; a header violation counts as met before launch 0) stores (j + 1) << 3 | VC_IRANS_ERR_* in
+     * ITS word and decodes zeros from that round on; every wave of the image decodes zeros in every LATER launch (a wave honours
+     * a sibling's word only when it was set in an earlier launch than the one it is running). */
+    uint32_t wave_error[VC_IRANS_MAX_WAVES];
+    uint32_t launches[VC_IRANS_MAX_WAVES]; /* vc_irans_decode launches this wave has run */
+    uint32_t pad[2];
+    uint64_t x[VC_IRANS_MAX_WAVES][64];
+} vc_irans_dstate;
+/* payloads: device buffer of u32; where [images][2] (device) = {first u32 of the image's payload, its length in bytes}.
+ * vc_irans_decode_begin reads the headers into states[images]; vc_irans_decode decodes one segment (one launch, grid =
+ * images x W): indexes / symbols_out dense [images][count] int32.  Neither can fault or hang on any payload: loops are
+ * counted by `count`, every word read is checked against the sub-stream's count (itself checked against the length),
+ * the symbol search stays inside the row; violations set `error`.  payload_words: u32 in `payloads` (every `where` entry is
+ * checked against it). */
+int vc_irans_decode_begin(vc_stream s, const uint32_t *payloads, size_t payload_words, const uint32_t *where, int images, int waves,
+                          vc_irans_dstate *states);
+int vc_irans_decode(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, const int32_t *indexes,
+                    size_t count, vc_irans_dtables tables, int32_t *symbols_out);
+
+/* ------------------------------------------------------------------------------------------
  * Entry points under the operator names SURVEY.md section 8(b) lists for the boundary.  Thin forwards to the
  * functions above (same kernels, same argument rules); a binding may use either spelling.
  * ---------------------------------------------------------------------------------------- */

@@ -11,6 +11,7 @@
 #include <numeric>
 #include <vector>
 #include "vc_hip.h"
+#include "rans_lanes.h"
 
 namespace {
 // every table must fit its row and hold at least one real bin + the escape bin
@@ -239,6 +240,206 @@ extern "C" int vc_pmf_to_quantized_cdf(const float *pmf, int n, int precision, u
         if (donor < i) for (int j = donor + 1; j <= i; ++j) --cdf[j];
         else for (int j = i + 1; j <= donor; ++j) ++cdf[j];
     }
+    return VC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Interleaved coder, host reference: the 64 W lanes emulated with loops over the per-lane steps of rans_lanes.h, which
+// the kernels of rans_device.hip run in lockstep.  The yardstick of those kernels and what the CPU tests exercise.
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" size_t vc_irans_wave_words(size_t count, int waves)
+{
+    if (!irl::waves_ok(waves)) return 0;
+    const size_t lanes = static_cast<size_t>(irl::kLanes) * waves;
+    return 3 * irl::kLanes * (count / lanes + (count % lanes != 0));
+}
+
+extern "C" size_t vc_irans_bound(size_t count, int waves)
+{
+    if (!irl::waves_ok(waves)) return 0;
+    return static_cast<size_t>(waves) * (VC_IRANS_SUBSTREAM_HEADER + 4 * vc_irans_wave_words(count, waves));
+}
+
+extern "C" long long vc_irans_pack_tables(const int32_t *cdfs, int n_tables, int cdf_stride, const int32_t *cdf_sizes,
+                                          const int32_t *offsets, uint16_t *cdf16_out, int32_t *rows_out)
+{
+    if (!cdfs || !cdf_sizes || !offsets || !tables_ok(cdf_sizes, n_tables, cdf_stride)) return VC_EINVAL;
+    long long total = 0;
+    for (int t = 0; t < n_tables; ++t) {
+        const int32_t *cdf = cdfs + static_cast<size_t>(t) * cdf_stride;
+        const int32_t n = cdf_sizes[t];
+        if (n > 65537 || cdf[0] != 0 || cdf[n - 1] != 65536) return VC_EINVAL;
+        int32_t mode = 0, widest = 0;
+        for (int32_t i = 0; i + 1 < n; ++i) {
+            if (cdf[i + 1] <= cdf[i]) return VC_EINVAL;               // every slot can be coded, none is wider than 65535
+            if (cdf[i + 1] - cdf[i] > widest) { widest = cdf[i + 1] - cdf[i]; mode = i; }
+        }
+        if (total + n > 0x7fffff00ll) return VC_EINVAL;
+        if (cdf16_out)
+            for (int32_t i = 0; i < n; ++i) cdf16_out[total + i] = static_cast<uint16_t>(cdf[i]);
+        if (rows_out) {
+            rows_out[4 * t + 0] = static_cast<int32_t>(total);
+            rows_out[4 * t + 1] = n;
+            rows_out[4 * t + 2] = offsets[t];
+            rows_out[4 * t + 3] = mode;
+        }
+        total += n;
+    }
+    const long long padded = (total + 7) / 8 * 8;
+    if (cdf16_out)
+        for (long long i = total; i < padded; ++i) cdf16_out[i] = 0;
+    return padded;
+}
+
+namespace {
+struct PackedSet {
+    std::vector<uint16_t> cdf16;
+    std::vector<irl::Row> rows;
+};
+
+int pack_sets(const vc_irans_tables *sets, int n_sets, std::vector<PackedSet> &packed)
+{
+    if (!sets || n_sets < 1) return VC_EINVAL;
+    packed.resize(static_cast<size_t>(n_sets));
+    for (int k = 0; k < n_sets; ++k) {
+        const vc_irans_tables &s = sets[k];
+        const long long n = vc_irans_pack_tables(s.cdfs, s.n_tables, s.cdf_stride, s.cdf_sizes, s.offsets, nullptr, nullptr);
+        if (n < 0) return static_cast<int>(n);
+        packed[k].cdf16.resize(static_cast<size_t>(n));
+        packed[k].rows.resize(static_cast<size_t>(s.n_tables));
+        static_assert(sizeof(irl::Row) == 4 * sizeof(int32_t), "Row is the [n_tables][4] int32 layout");
+        vc_irans_pack_tables(s.cdfs, s.n_tables, s.cdf_stride, s.cdf_sizes, s.offsets, packed[k].cdf16.data(),
+                             reinterpret_cast<int32_t *>(packed[k].rows.data()));
+    }
+    return VC_OK;
+}
+
+bool segments_ok(const vc_irans_segment *segs, int n_segs, int n_sets)
+{
+    if (n_segs < 0 || (n_segs && !segs)) return false;
+    for (int s = 0; s < n_segs; ++s) {
+        if (segs[s].table_set < 0 || segs[s].table_set >= n_sets) return false;
+        if (segs[s].count && (!segs[s].symbols || !segs[s].indexes)) return false;
+    }
+    return true;
+}
+
+struct WordsAt {                               // u32 i of a byte buffer of any alignment
+    const uint8_t *p;
+    uint32_t operator()(uint64_t i) const
+    {
+        uint32_t w;
+        std::memcpy(&w, p + 4 * i, 4);
+        return w;
+    }
+};
+}  // namespace
+
+extern "C" long long vc_irans_encode_host(const vc_irans_segment *segs, int n_segs, const vc_irans_tables *sets, int n_sets, int waves,
+                                          uint8_t *out, size_t out_cap)
+{
+    if (!out || !irl::waves_ok(waves) || !segments_ok(segs, n_segs, n_sets)) return VC_EINVAL;
+    std::vector<PackedSet> packed;
+    if (const int rc = pack_sets(sets, n_sets, packed)) return rc;
+    const size_t lanes = static_cast<size_t>(irl::kLanes) * waves;
+    std::vector<uint64_t> x(lanes, irl::kLow);
+    std::vector<std::vector<uint32_t>> emitted(static_cast<size_t>(waves));    // per wave, in the order the encoder emits: the decoder's, reversed
+    for (int s = n_segs; s-- > 0;) {
+        const vc_irans_segment &seg = segs[s];
+        const PackedSet &set = packed[seg.table_set];
+        const int n_tables = static_cast<int>(set.rows.size());
+        for (size_t i = 0; i < seg.count; ++i)
+            if (static_cast<uint32_t>(seg.indexes[i]) >= static_cast<uint32_t>(n_tables)) return VC_EINVAL;
+        const size_t rounds = seg.count / lanes + (seg.count % lanes != 0);
+        for (size_t r = rounds; r-- > 0;)
+            for (int step = 2; step >= 0; --step)             // high half, low half, the symbol's slot: the decoder's three sub-steps backwards
+                for (size_t g = lanes; g-- > 0;) {            // descending lanes: the decoder takes its words in ascending lane order
+                    const size_t i = r * lanes + g;
+                    if (i >= seg.count) continue;
+                    const irl::Row &row = set.rows[seg.indexes[i]];
+                    const uint16_t *cdf = set.cdf16.data() + row.start;
+                    bool escaped;
+                    const int slot = irl::slot_of(seg.symbols[i], row, escaped);
+                    if (step && !escaped) continue;
+                    const uint32_t zz = irl::zigzag(seg.symbols[i], row.offset);
+                    const uint32_t start = step == 2 ? zz >> 16 : step == 1 ? (zz & 0xffffu) : irl::slot_start(cdf, slot);
+                    const uint32_t freq = step ? 1u : irl::slot_freq(cdf, slot);
+                    if (irl::put_emits(x[g], freq)) {
+                        emitted[g / irl::kLanes].push_back(static_cast<uint32_t>(x[g]));
+                        x[g] >>= 32;
+                    }
+                    x[g] = irl::put(x[g], start, freq);
+                }
+    }
+    size_t need = 0;
+    for (const auto &e : emitted) need += VC_IRANS_SUBSTREAM_HEADER + 4 * e.size();
+    if (need > out_cap) return VC_ENOMEM;
+    uint8_t *p = out;
+    for (int w = 0; w < waves; ++w) {
+        const std::vector<uint32_t> &e = emitted[w];
+        if (e.size() > 0xffffffffull) return VC_EINVAL;
+        const uint32_t count = static_cast<uint32_t>(e.size());
+        std::memcpy(p, &count, 4);
+        std::memcpy(p + 4, x.data() + static_cast<size_t>(w) * irl::kLanes, 8 * irl::kLanes);
+        p += VC_IRANS_SUBSTREAM_HEADER;
+        for (size_t k = e.size(); k-- > 0; p += 4) std::memcpy(p, &e[k], 4);
+    }
+    return static_cast<long long>(need);
+}
+
+extern "C" int vc_irans_decode_host(const uint8_t *data, size_t nbytes, const vc_irans_segment *segs, int n_segs,
+                                    const vc_irans_tables *sets, int n_sets, int waves)
+{
+    if (!data || !irl::waves_ok(waves) || !segments_ok(segs, n_segs, n_sets)) return VC_EINVAL;
+    std::vector<PackedSet> packed;
+    if (const int rc = pack_sets(sets, n_sets, packed)) return rc;
+    if (nbytes % 4) return VC_EDATA;
+    const WordsAt word{data};
+    uint32_t base[VC_IRANS_MAX_WAVES], count[VC_IRANS_MAX_WAVES], cursor[VC_IRANS_MAX_WAVES] = {};
+    if (!irl::walk_headers(word, nbytes / 4, waves, 0, base, count)) return VC_EDATA;
+    const size_t lanes = static_cast<size_t>(irl::kLanes) * waves;
+    std::vector<uint64_t> x(lanes);
+    for (size_t g = 0; g < lanes; ++g) {
+        const uint64_t at = base[g / irl::kLanes] - irl::kHeaderWords + 1 + 2 * (g % irl::kLanes);
+        x[g] = static_cast<uint64_t>(word(at)) | (static_cast<uint64_t>(word(at + 1)) << 32);
+    }
+    std::vector<uint8_t> escaped(lanes);
+    std::vector<uint32_t> low(lanes);
+    for (int s = 0; s < n_segs; ++s) {
+        const vc_irans_segment &seg = segs[s];
+        const PackedSet &set = packed[seg.table_set];
+        const int n_tables = static_cast<int>(set.rows.size());
+        const size_t rounds = seg.count / lanes + (seg.count % lanes != 0);
+        for (size_t r = 0; r < rounds; ++r)
+            for (int step = 0; step < 3; ++step)
+                for (size_t g = 0; g < lanes; ++g) {
+                    const size_t i = r * lanes + g;
+                    if (i >= seg.count) continue;
+                    if (step && !escaped[g]) continue;
+                    const int32_t t = seg.indexes[i];
+                    if (static_cast<uint32_t>(t) >= static_cast<uint32_t>(n_tables)) return VC_EINVAL;
+                    const irl::Row &row = set.rows[t];
+                    if (step == 0) {
+                        const uint16_t *cdf = set.cdf16.data() + row.start;
+                        const int slot = irl::lookup(cdf, row.size, row.mode, irl::cum_of(x[g]));
+                        x[g] = irl::get(x[g], irl::slot_start(cdf, slot), irl::slot_freq(cdf, slot));
+                        escaped[g] = slot == row.size - 2;
+                        seg.symbols[i] = irl::symbol_of(slot, row.offset);
+                    } else {
+                        const uint32_t half = irl::cum_of(x[g]);
+                        x[g] = irl::get(x[g], half, 1u);
+                        if (step == 1) low[g] = half;
+                        else seg.symbols[i] = irl::unzigzag(low[g] | (half << 16), row.offset);
+                    }
+                    if (irl::needs_word(x[g])) {
+                        const int w = static_cast<int>(g / irl::kLanes);
+                        if (cursor[w] >= count[w]) return VC_EDATA;
+                        x[g] = irl::take_word(x[g], word(static_cast<uint64_t>(base[w]) + cursor[w]++));
+                    }
+                }
+    }
+    for (int w = 0; w < waves; ++w)
+        if (cursor[w] != count[w]) return VC_EDATA;
     return VC_OK;
 }
 

@@ -271,3 +271,53 @@ def unpack_icip2024_frame(data):
         pos += n
     strings = {"offset": [[[p] for p in parts[1:6]], [parts[0]]], "residual": [[[p] for p in parts[7:12]], [parts[6]]]}
     return {"strings": strings, "shape": (hz, wz), "down_ratio": down_ratio, "s": s, "scale1": scale1, "scale2": scale2}
+
+
+# Container of the device-coded frames (FlowGuidedB.compress(coder="device"); payload format: DESIGN.md section 4d).  Its own
+# magic: a VCIB reader refuses it and this reader refuses VCIB.  Little-endian:
+#   offset  0  the 22 header bytes of VCIB with magic "VCID": version (1), down_ratio, hyper-latent shape, s, scale1, scale2
+#          22  u8       waves W (1, 2, 4, 8 or 16): sub-streams per payload
+#          23  u32 x 2  payload lengths: offset, residual
+#          31  the two payloads in that order
+ICIP2024_DEV_MAGIC = b"VCID"
+ICIP2024_DEV_TAIL = struct.Struct("<BII")
+
+
+def pack_icip2024_frame_dev(strings, shape, down_ratio, s, scale1, scale2, waves, image=0):
+    """The container of image ``image`` of a ``FlowGuidedB.compress(coder="device")`` result (``waves`` as it returns it)."""
+    hz, wz = int(shape[0]), int(shape[1])
+    if int(down_ratio) not in ICIP2024_DOWN_RATIOS or not (1 <= hz <= 0xffff and 1 <= wz <= 0xffff) or not hip.irans_waves_ok(waves):
+        raise hip.VcError(f"down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} / waves {waves} do not fit the container")
+    if not isinstance(strings, dict) or set(strings) != {"offset", "residual"}:
+        raise hip.VcError('strings: {"offset": [payload per image], "residual": [payload per image]}')
+    payloads = [bytes(strings[c][image]) for c in ("offset", "residual")]
+    if any(len(p) > 0xffffffff for p in payloads):
+        raise hip.VcError("a payload is longer than the container's 32-bit length field")
+    head = ICIP2024_HEADER.pack(ICIP2024_DEV_MAGIC, ICIP2024_VERSION, int(down_ratio), hz, wz, float(s), float(scale1), float(scale2))
+    return head + ICIP2024_DEV_TAIL.pack(int(waves), *(len(p) for p in payloads)) + b"".join(payloads)
+
+
+def unpack_icip2024_frame_dev(data):
+    """Inverse of :func:`pack_icip2024_frame_dev`: ``{"strings" (one image per list), "waves", "shape", "down_ratio", "s", "scale1",
+    "scale2"}``; magic, version, field ranges, the wave count, the smallest possible payload and the total length are validated
+    before anything is returned (VcError)."""
+    data = bytes(data)
+    fixed = ICIP2024_HEADER.size + ICIP2024_DEV_TAIL.size
+    if len(data) < fixed:
+        raise hip.VcError(f"ICIP2024 device-coded container: {len(data)} bytes is shorter than the {fixed}-byte header")
+    magic, version, down_ratio, hz, wz, s, scale1, scale2 = ICIP2024_HEADER.unpack_from(data, 0)
+    if magic != ICIP2024_DEV_MAGIC:
+        raise hip.VcError(f"ICIP2024 device-coded container: magic {magic!r} is not {ICIP2024_DEV_MAGIC!r}")
+    if version != ICIP2024_VERSION:
+        raise hip.VcError(f"ICIP2024 device-coded container: version {version} (this reader knows {ICIP2024_VERSION})")
+    if down_ratio not in ICIP2024_DOWN_RATIOS or hz < 1 or wz < 1:
+        raise hip.VcError(f"ICIP2024 device-coded container: down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} out of range")
+    if not all(np.isfinite(v) for v in (s, scale1, scale2)):
+        raise hip.VcError("ICIP2024 device-coded container: a header number is not finite")
+    waves, n_off, n_res = ICIP2024_DEV_TAIL.unpack_from(data, ICIP2024_HEADER.size)
+    if not hip.irans_waves_ok(waves):
+        raise hip.VcError(f"ICIP2024 device-coded container: waves {waves} is not a power of two in 1..16")
+    if fixed + n_off + n_res != len(data) or min(n_off, n_res) < waves * hip.IRANS_SUBSTREAM_HEADER or n_off % 4 or n_res % 4:
+        raise hip.VcError(f"ICIP2024 device-coded container: payload lengths {n_off} + {n_res} do not fit {len(data)} bytes / {waves} waves")
+    strings = {"offset": [data[fixed:fixed + n_off]], "residual": [data[fixed + n_off:]]}
+    return {"strings": strings, "waves": waves, "shape": (hz, wz), "down_ratio": down_ratio, "s": s, "scale1": scale1, "scale2": scale2}

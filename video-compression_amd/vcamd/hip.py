@@ -8,6 +8,7 @@ import contextlib
 import ctypes
 import functools
 import os
+import threading
 
 import numpy as np
 import torch
@@ -60,6 +61,34 @@ class RefineLayer(ctypes.Structure):
 
 
 _lib = None
+
+
+class IransTablesC(ctypes.Structure):
+    """vc_irans_tables: one host table set"""
+    _fields_ = [("cdfs", ctypes.c_void_p), ("n_tables", ctypes.c_int), ("cdf_stride", ctypes.c_int),
+                ("cdf_sizes", ctypes.c_void_p), ("offsets", ctypes.c_void_p)]
+
+
+class IransSegmentC(ctypes.Structure):
+    """vc_irans_segment (host)"""
+    _fields_ = [("symbols", ctypes.c_void_p), ("indexes", ctypes.c_void_p), ("count", ctypes.c_size_t), ("table_set", ctypes.c_int)]
+
+
+class IransDTables(ctypes.Structure):
+    """vc_irans_dtables: device copies of a packed table set"""
+    _fields_ = [("cdf16", ctypes.c_void_p), ("rows", ctypes.c_void_p), ("n_tables", ctypes.c_int), ("entries", ctypes.c_int)]
+
+
+class IransDSegment(ctypes.Structure):
+    """vc_irans_dsegment (device tensors)"""
+    _fields_ = [("symbols", ctypes.c_void_p), ("indexes", ctypes.c_void_p), ("count", ctypes.c_uint32), ("table_set", ctypes.c_int)]
+
+
+IRANS_MAX_WAVES = 16
+IRANS_SUBSTREAM_HEADER = 516
+IRANS_STATE_HEADER_WORDS = 2 + 5 * IRANS_MAX_WAVES + 2              # vc_irans_dstate in front of its states
+IRANS_STATE_BYTES = 4 * IRANS_STATE_HEADER_WORDS + 8 * 64 * IRANS_MAX_WAVES
+IRANS_ERRORS = {1: "sub-stream headers / word counts do not fit the payload", 2: "a sub-stream ended early", 4: "table index out of range"}
 
 
 class KernelTimer:
@@ -197,6 +226,15 @@ def lib():
     sig("vc_rans_encode_with_indexes", cll, vp, vp, sz, vp, ci, ci, vp, vp, vp, sz)
     sig("vc_rans_decode_with_indexes", ci, vp, sz, vp, sz, vp, ci, ci, vp, vp, vp)
     sig("vc_rans_decode_stream", ci, vp, sz, vp, vp, sz, vp, ci, ci, vp, vp, vp)
+    sig("vc_irans_bound", sz, sz, ci)
+    sig("vc_irans_wave_words", sz, sz, ci)
+    sig("vc_irans_encode_host", cll, vp, ci, vp, ci, ci, vp, sz)
+    sig("vc_irans_decode_host", ci, vp, sz, vp, ci, vp, ci, ci)
+    sig("vc_irans_pack_tables", cll, vp, ci, ci, vp, vp, vp, vp)
+    sig("vc_irans_tables_in_lds", ci, ci)
+    sig("vc_irans_encode", ci, vp, vp, ci, vp, ci, ci, ci, vp, sz, vp)
+    sig("vc_irans_decode_begin", ci, vp, vp, sz, vp, ci, ci, vp)
+    sig("vc_irans_decode", ci, vp, vp, vp, ci, ci, vp, sz, IransDTables, vp)
     _lib = L
     return L
 
@@ -212,6 +250,8 @@ EXPORTED_SYMBOLS = [
     "vc_attention_gate", "vc_sse_clamp01", "vc_select_flow", "vc_eb_forward", "vc_eb_dequant", "vc_gc_forward", "vc_gc_indexes", "vc_refine_scales",
     "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_gc_forward_ckbd", "vc_gc_indexes_ckbd", "vc_gc_dequant_ckbd", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
+    "vc_irans_bound", "vc_irans_wave_words", "vc_irans_encode_host", "vc_irans_decode_host", "vc_irans_pack_tables",
+    "vc_irans_tables_in_lds", "vc_irans_encode", "vc_irans_decode_begin", "vc_irans_decode",
     # the operator spellings of SURVEY.md 8(b), thin forwards (csrc/abi_aliases.cpp)
     "vc_gdn", "vc_spynet_level", "vc_pool", "vc_upsample", "vc_pad", "vc_blend", "vc_factorized_bits", "vc_gaussian_symbols",
 ]
@@ -1144,3 +1184,193 @@ class RansStreamDecoder:
                                           cdfs.ctypes.data, cdfs.shape[0], cdfs.shape[1], sizes.ctypes.data, offs.ctypes.data,
                                           out.ctypes.data), "vc_rans_decode_stream")
         return out
+
+
+# ------------------------------------------------------------------------------------------------
+# interleaved range coder (include/vc_hip.h): host reference and device kernels
+# ------------------------------------------------------------------------------------------------
+def irans_waves_ok(waves):
+    return isinstance(waves, (int, np.integer)) and 1 <= waves <= IRANS_MAX_WAVES and (waves & (waves - 1)) == 0
+
+
+def _irans_host_args(segments, table_sets, writable):
+    """segments: [(symbols, indexes, table_set)] (decoder: symbols = None, allocated here); table_sets: [(cdfs, sizes, offsets)]"""
+    keep, sets = [], (IransTablesC * max(len(table_sets), 1))()
+    for k, ts in enumerate(table_sets):
+        cdfs, sizes, offs = _tables(*ts)
+        keep.append((cdfs, sizes, offs))
+        sets[k] = IransTablesC(cdfs.ctypes.data, cdfs.shape[0], cdfs.shape[1], sizes.ctypes.data, offs.ctypes.data)
+    segs = (IransSegmentC * max(len(segments), 1))()
+    arrays = []
+    for k, (sym, idx, which) in enumerate(segments):
+        idx = _i32(idx).reshape(-1)
+        sym = np.empty(idx.size, dtype=np.int32) if writable else _i32(sym).reshape(-1)
+        if sym.size != idx.size:
+            raise VcError("range coder: one table index per symbol")
+        arrays.append((sym, idx))
+        segs[k] = IransSegmentC(sym.ctypes.data, idx.ctypes.data, idx.size, int(which))
+    return segs, sets, arrays, keep
+
+
+def irans_encode_host(segments, table_sets, waves=4):
+    """Host reference encoder: ``segments`` = [(symbols, indexes, table_set)], ``table_sets`` = [(cdfs, cdf_sizes, offsets)];
+    returns the payload (bytes)."""
+    segs, sets, arrays, keep = _irans_host_args(segments, table_sets, False)
+    cap = sum(lib().vc_irans_bound(sym.size, int(waves)) for sym, _ in arrays) or lib().vc_irans_bound(0, int(waves))
+    out = np.empty(max(cap, 4) // 4, dtype=np.uint32)
+    n = lib().vc_irans_encode_host(segs, len(segments), sets, len(table_sets), int(waves), out.ctypes.data, cap)
+    if n < 0:
+        check(int(n), "vc_irans_encode_host")
+    return out.view(np.uint8)[:n].tobytes()
+
+
+def irans_decode_host(data, segments, table_sets, waves=4):
+    """Host reference decoder: ``segments`` = [(indexes, table_set)]; returns one int32 array per segment."""
+    segs, sets, arrays, keep = _irans_host_args([(None, idx, which) for idx, which in segments], table_sets, True)
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    check(lib().vc_irans_decode_host(buf.ctypes.data if buf.size else None, buf.size, segs, len(segments), sets, len(table_sets), int(waves)),
+          "vc_irans_decode_host")
+    return [sym for sym, _ in arrays]
+
+
+class IransTables:
+    """A table set packed for the kernels (vc_irans_pack_tables) and resident on ``device``: the used entries of every cdf row as
+    u16 and per table (first entry, cdf_size, offset, mode).  The entropy models cache one and drop it in update()."""
+
+    def __init__(self, cdfs, cdf_sizes, offsets, device):
+        cdfs, sizes, offs = _tables(cdfs, cdf_sizes, offsets)
+        args = (cdfs.ctypes.data, cdfs.shape[0], cdfs.shape[1], sizes.ctypes.data, offs.ctypes.data)
+        n = lib().vc_irans_pack_tables(*args, None, None)
+        if n < 0:
+            check(int(n), "vc_irans_pack_tables")
+        cdf16 = np.empty(n, dtype=np.uint16)
+        rows = np.empty((cdfs.shape[0], 4), dtype=np.int32)
+        lib().vc_irans_pack_tables(*args, cdf16.ctypes.data, rows.ctypes.data)
+        self.entries, self.n_tables = int(n), int(cdfs.shape[0])
+        self.cdf16 = torch.from_numpy(cdf16.view(np.int16)).to(device)
+        self.rows = torch.from_numpy(rows).to(device)
+        self.in_lds = bool(lib().vc_irans_tables_in_lds(self.entries))
+
+    def struct(self):
+        return IransDTables(self.cdf16.data_ptr(), self.rows.data_ptr(), self.n_tables, self.entries)
+
+
+def irans_encode(segments, table_sets, waves=4):
+    """Device encoder (vc_irans_encode): ``segments`` = [(symbols, indexes, table_set)] of int32 CUDA tensors [images, count],
+    ``table_sets`` = [IransTables].  One launch, one read of the images x W word counts, one copy of the used tails; returns one
+    payload (bytes) per image."""
+    if not segments or not irans_waves_ok(waves):
+        raise VcError("irans_encode: at least one segment, waves a power of two in 1..16")
+    images, dev = int(segments[0][0].shape[0]), segments[0][0].device
+    segs = (IransDSegment * len(segments))()
+    cap = 0
+    for k, (sym, idx, which) in enumerate(segments):
+        if sym.dtype != torch.int32 or idx.dtype != torch.int32 or sym.shape != idx.shape or sym.dim() != 2 or sym.shape[0] != images \
+                or not (sym.is_contiguous() and idx.is_contiguous() and sym.is_cuda and idx.is_cuda):
+            raise VcError("irans_encode: symbols / indexes are dense int32 CUDA tensors [images, count]")
+        segs[k] = IransDSegment(sym.data_ptr(), idx.data_ptr(), int(sym.shape[1]), int(which))
+        cap += lib().vc_irans_wave_words(int(sym.shape[1]), int(waves))
+    sets = (IransDTables * len(table_sets))(*[t.struct() for t in table_sets])
+    region = IRANS_SUBSTREAM_HEADER // 4 + cap
+    out = torch.empty((images * waves, region), dtype=torch.int32, device=dev)
+    counts = torch.empty(images * waves, dtype=torch.int32, device=dev)
+    check(lib().vc_irans_encode(stream(), segs, len(segments), sets, len(table_sets), images, int(waves), out.data_ptr(), cap,
+                                counts.data_ptr()), "vc_irans_encode")
+    used = counts.cpu().numpy().astype(np.int64) & 0xffffffff          # the one synchronisation
+    if (used == 0xffffffff).any():
+        raise VcError("vc_irans_encode: a table index is out of range")
+    tails = torch.cat([out[k, cap - int(c):] for k, c in enumerate(used)]).cpu().numpy().tobytes()
+    sizes = IRANS_SUBSTREAM_HEADER + 4 * used.reshape(images, waves)
+    ends = np.concatenate([[0], np.cumsum(sizes.sum(axis=1))])
+    return [tails[ends[j]:ends[j + 1]] for j in range(images)]
+
+
+class _PinnedStage:
+    """Pinned host staging for the payload uploads, reused from call to call (pinning is an allocation of its own and costs more
+    than the copy): two buffers in turn, each guarded by an event recorded behind the asynchronous copy that last read it."""
+
+    def __init__(self):
+        self.slots = [[None, None], [None, None]]                      # [pinned uint8 tensor, event of its last copy]
+        self.turn = 0
+        self.lock = threading.Lock()                                     # held from take() to release(): one upload fills a slot at a time
+
+    def take(self, nbytes):
+        self.lock.acquire()
+        self.turn ^= 1
+        slot = self.slots[self.turn]
+        if slot[1] is not None:
+            slot[1].synchronize()                                        # (a copy enqueued two uploads ago: long done)
+        if slot[0] is None or slot[0].numel() < nbytes:
+            slot[0] = torch.empty(max(1 << 20, 1 << (int(nbytes) - 1).bit_length()), dtype=torch.uint8).pin_memory()
+        return slot
+
+    def release(self, slot):
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        self.lock.release()
+
+
+_stage = _PinnedStage()
+
+
+class IransDecoder:
+    """Device decoder of one payload per image: uploads the payloads once (pinned, non-blocking), reads the sub-stream headers
+    into the device state (vc_irans_decode_begin), then :meth:`decode` is one launch per segment and nothing comes back to the
+    host until :meth:`finish` reads the states' error words and cursors -- one copy, after everything that used the symbols.
+    The constructor stages the payloads in pinned memory shared by the whole process (two buffers in turn, under a lock, so
+    threads may build decoders concurrently): before it refills a buffer it waits on the host for the copy that last read it,
+    enqueued two uploads earlier -- the one place this class may block, and it lies in front of the launches-only part."""
+
+    def __init__(self, payloads, waves, device):
+        if not payloads or not irans_waves_ok(waves):
+            raise VcError("IransDecoder: at least one payload, waves a power of two in 1..16")
+        self.images, self.waves = len(payloads), int(waves)
+        where, pos = np.zeros((self.images, 2), dtype=np.int64), 0
+        for j, p in enumerate(payloads):
+            where[j] = (pos, len(p))
+            pos += -(-len(p) // 16) * 4 + 4                              # every payload starts on a 16-byte boundary
+        if pos > 0x7fffffff or max(len(p) for p in payloads) > 0xffffffff:
+            raise VcError("IransDecoder: the payloads exceed the 32-bit word offsets of the format")
+        nbytes = 4 * pos + 4 * where.size
+        slot = _stage.take(nbytes)
+        try:
+            view = slot[0].numpy()
+            for j, p in enumerate(payloads):                             # (the padding between payloads is never read)
+                view[4 * where[j, 0]:4 * where[j, 0] + len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
+            view[4 * pos:nbytes] = where.astype(np.uint32).reshape(-1).view(np.uint8)
+            self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            self.buf.copy_(slot[0][:nbytes], non_blocking=True)
+        finally:
+            _stage.release(slot)
+        self.words = pos
+        self.states = torch.empty(self.images * IRANS_STATE_BYTES, dtype=torch.uint8, device=device)
+        check(lib().vc_irans_decode_begin(stream(), self.buf.data_ptr(), pos, self.buf.data_ptr() + 4 * pos, self.images, self.waves,
+                                          self.states.data_ptr()), "vc_irans_decode_begin")
+
+    def decode(self, indexes, tables, out=None):
+        """indexes: int32 CUDA tensor [images, count]; returns the symbols, same shape (``out`` when given)."""
+        if indexes.dtype != torch.int32 or indexes.dim() != 2 or indexes.shape[0] != self.images or not indexes.is_contiguous():
+            raise VcError("IransDecoder.decode: indexes is a dense int32 tensor [images, count]")
+        if out is None:
+            out = torch.empty_like(indexes)
+
+        def launch():
+            check(lib().vc_irans_decode(stream(), self.buf.data_ptr(), self.states.data_ptr(), self.images, self.waves, indexes.data_ptr(),
+                                        int(indexes.shape[1]), tables.struct(), out.data_ptr()), "vc_irans_decode")
+        if timer is None:
+            launch()
+        else:                                  # (tools/icip_codec_bench.py: the decode kernels alone, from HIP events)
+            timer.bracket("irans decode", 0.0, launch, 8.0 * indexes.numel())
+        return out
+
+    def finish(self):
+        """The one read: VcError when a violation was met or a sub-stream was not consumed to its last word."""
+        head = self.states.view(self.images, IRANS_STATE_BYTES)[:, :4 * IRANS_STATE_HEADER_WORDS].cpu().numpy().view(np.uint32)
+        for j in range(self.images):
+            err = int(head[j, 0])
+            if err:
+                what = "; ".join(v for k, v in IRANS_ERRORS.items() if err & k)
+                raise VcError(f"interleaved range decoder, image {j}: {what} (the symbols behind the violation are zeros)")
+            count, cursor = head[j, 2 + 16:2 + 16 + self.waves], head[j, 2 + 32:2 + 32 + self.waves]
+            if not np.array_equal(count, cursor):
+                raise VcError(f"interleaved range decoder, image {j}: consumed {cursor.tolist()} of {count.tolist()} words")

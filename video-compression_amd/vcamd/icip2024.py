@@ -506,12 +506,19 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         trace["y_hat"] = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
         trace["z_hat"] = hip.nhwc_to_nchw(z_hat)
 
-    def compress_t(self, enc1, enc2, enc3, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None):
+    def _z_index_dev(self, n, hw, dev):
+        """table index of every hyper-latent symbol, [n, N * hw] on the device: the channel (no synchronisation)"""
+        return torch.arange(self.N, dtype=torch.int32, device=dev).view(1, self.N, 1).expand(n, self.N, hw).reshape(n, -1).contiguous()
+
+    def compress_t(self, enc1, enc2, enc3, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None, coder="host", waves=4):
         """Encoder of the bitstream path on channels-last views (arguments as :meth:`code`).  Returns ``{"strings": [[[g0 per
         image], ..., [g4 per image]], [z per image]], "shape": (hz, wz), "heads": the three decoder heads computed from the y_hat
         the decoder rebuilds (closed loop), "bits": 0-dim float64 device tensor, the -log2 p sum of exactly the coded symbols (the
         z row + two parity rows per group)}``.  ``trace``: receives "y_hat" (five NCHW tensors, gained domain), "z_hat" and
-        "passes" (per pass a dict group / c0 / c1 / parity / y / scales / means of views)."""
+        "passes" (per pass a dict group / c0 / c1 / parity / y / scales / means of views) and "coded" (the segment table: (symbols,
+        indexes) int32 device tensors [n, count] of z and of the ten passes in coding order).  ``coder="device"``: "strings" is
+        one payload per image of the interleaved coder instead (hyper-latent segment, then the ten passes),
+        coded by one launch of vc_irans_encode on the integers where they lie."""
         L, M = hip.lib(), self.M
         gain, hypergain, invhypergain, invgain = self.interpolate_gain(s)
         y = self.seq_cat("g_a1", enc1) if len(enc1) > 1 else self.seq("g_a1", enc1[0])
@@ -546,6 +553,16 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
                                         "means": means})
         heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
         total = bits.totals().sum()
+        device = coder == "device"
+        z_index_dev = self._z_index_dev(n, z.h * z.w, dev) if device or trace is not None else None
+        if trace is not None:
+            self._trace_latents(trace, y_hat, z_hat)
+            trace["heads"] = heads
+            trace["coded"] = [(z_sym, z_index_dev)] + [p for passes in coded for p in passes]
+        if device:
+            segments = [(z_sym, z_index_dev, 0)] + [(sym, idx, 1) for passes in coded for sym, idx in passes]
+            payloads = hip.irans_encode(segments, [self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()], waves)
+            return {"strings": payloads, "shape": (z.h, z.w), "heads": heads, "bits": total}
         # the only device -> host traffic of the pass: squeezed int32 tensors (one synchronisation, after the last launch)
         eb_tables = self.entropy_bottleneck.tables()
         gc_tables = self.gaussian_conditional.tables()
@@ -556,9 +573,6 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
             host = [(sym.cpu().numpy(), idx.cpu().numpy()) for sym, idx in passes]
             strings.append([hip.rans_encode(np.concatenate([sy[j] for sy, _ in host]), np.concatenate([ix[j] for _, ix in host]),
                                             *gc_tables) for j in range(n)])
-        if trace is not None:
-            self._trace_latents(trace, y_hat, z_hat)
-            trace["heads"] = heads
         return {"strings": [strings, z_strings], "shape": (z.h, z.w), "heads": heads, "bits": total}
 
     def decompress_t(self, strings, shape, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None):
@@ -568,6 +582,8 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         dev = self.Gain.device
         _, _, invhypergain, invgain = self.interpolate_gain(s)
         hz, wz = int(shape[0]), int(shape[1])
+        if isinstance(strings, hip.IransDecoder):
+            return self._decompress_t_uploaded(strings, hz, wz, f1d, f2d, f3d, temporal_into, invhypergain, invgain, res, trace)
         if len(strings) != 2 or len(strings[0]) != 5 or not strings[1] or any(len(g) != len(strings[1]) for g in strings[0]):
             raise hip.VcError("strings: [[g0, ..., g4], z] with one byte string per image in each of the six lists")
         if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
@@ -594,6 +610,36 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
             idx_host = idx.cpu().numpy()
             sym = torch.from_numpy(np.stack([decoders[j].decode_stream(idx_host[j], *gc_tables) for j in range(n)])).to(dev)
             keep.append(sym)                                           # (must outlive the launch that reads it)
+            hip.check(L.vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None, parity, y_hat.channels(c0, c1).view()),
+                      "vc_gc_dequant_ckbd")
+        heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
+        if trace is not None:
+            self._trace_latents(trace, y_hat, z_hat)
+            trace["heads"] = heads
+        return heads
+
+    def _decompress_t_uploaded(self, dec, hz, wz, f1d, f2d, f3d, temporal_into, invhypergain, invgain, res, trace):
+        """decompress_t on the payloads of ``coder="device"``, already uploaded (hip.IransDecoder): every pass is vc_gc_indexes_ckbd ->
+        vc_irans_decode -> vc_gc_dequant_ckbd on the device, nothing crosses to the host (the caller reads the decoder's error
+        words once, after the reconstruction)."""
+        L, M = hip.lib(), self.M
+        dev = self.Gain.device
+        if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
+            raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
+        n, h, w = dec.images, 4 * hz, 4 * wz
+        table = self._scale_table_dev()
+        eb_tables, gc_tables = self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()
+        z_sym = dec.decode(self._z_index_dev(n, hz * wz, dev), eb_tables)
+        z_hat = T.empty(n, hz, wz, self.N, dev)
+        hip.check(L.vc_eb_dequant(hip.stream(), z_sym.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
+                                  invhypergain.data_ptr(), z_hat.view()), "vc_eb_dequant")
+        pin0, pin = self._hyper_buffers(z_hat, temporal_into)
+        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
+        for i, c0, c1, parity, scales, means in self._group_passes(pin0, pin, y_hat):
+            idx = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
+            hip.check(L.vc_gc_indexes_ckbd(hip.stream(), scales.view(), parity, table.data_ptr(), table.numel(), idx.data_ptr()),
+                      "vc_gc_indexes_ckbd")
+            sym = dec.decode(idx, gc_tables)                           # (torch's allocator keeps the block until the stream is past it)
             hip.check(L.vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None, parity, y_hat.channels(c0, c1).view()),
                       "vc_gc_dequant_ckbd")
         heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
@@ -1052,7 +1098,8 @@ class FlowGuidedB(nn.Module):
     # -- real bitstream (this project's own format: the reference has none for this model) ----------------
     SEARCH_RATIOS = (1, 2, 4, 8, 16)
 
-    def _bitstream_pass(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio, strings=None, shape=None, trace=None):
+    def _bitstream_pass(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio, strings=None, shape=None, trace=None, coder="host",
+                        waves=4):
         """The stages of :meth:`forward_device` with the two compressors on their bitstream paths; ``xcur`` is None on the decoder,
         which runs the reference-only stages through the same launches on the same buffer layouts (the per-level buffers keep
         their fcur slice, unused): every tensor the entropy path reads comes out of the same kernel instances on both sides."""
@@ -1084,7 +1131,8 @@ class FlowGuidedB(nn.Module):
         off_cond = lambda dst: self.offset_temporal_conditioner.run(cond[0], cond[1], cond[2], out=dst)  # noqa: E731
         out = {}
         if enc:
-            out["offset"] = oc.compress_t([F_[0]], [F_[1]], [F_[2]], cond[0], cond[1], cond[2], off_cond, s, trace=t_off)
+            out["offset"] = oc.compress_t([F_[0]], [F_[1]], [F_[2]], cond[0], cond[1], cond[2], off_cond, s, trace=t_off, coder=coder,
+                                          waves=waves)
             offs = out["offset"]["heads"]
         else:
             offs = oc.decompress_t(strings["offset"], shape, cond[0], cond[1], cond[2], off_cond, s, trace=t_off)
@@ -1096,7 +1144,7 @@ class FlowGuidedB(nn.Module):
         res_cond = lambda dst: self.residue_temporal_conditioner.run(comp[0], comp[1], comp[2], out=dst)  # noqa: E731
         if enc:
             out["residual"] = rc.compress_t([fcur[0], comp[0]], [fcur[1], comp[1]], [fcur[2], comp[2]], comp[0], comp[1], comp[2],
-                                            res_cond, s, res=tuple(comp), trace=t_res)
+                                            res_cond, s, res=tuple(comp), trace=t_res, coder=coder, waves=waves)
             xs = out["residual"]["heads"]
         else:
             xs = rc.decompress_t(strings["residual"], shape, comp[0], comp[1], comp[2], res_cond, s, res=tuple(comp), trace=t_res)
@@ -1110,15 +1158,26 @@ class FlowGuidedB(nn.Module):
         """the quality level as the container stores it (fp32): both sides interpolate the gains from the same number"""
         return float(np.float32(s))
 
-    def compress(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio=None, trace=None):
+    CODERS = ("host", "device")
+
+    def _check_coder(self, coder, waves):
+        if coder not in self.CODERS or not hip.irans_waves_ok(waves):
+            raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {self.CODERS}, waves a power of two in 1..16")
+
+    def compress(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio=None, trace=None, coder="host", waves=4):
         """Encode a B-frame for real.  NCHW CUDA tensors and host numbers as :meth:`forward`; ``down_ratio=None`` searches the
         flow resolution on the device (:meth:`search_flow_t`) and reads the choice to the host.  Returns ``{"strings": {"offset",
         "residual"} each [[[g0], ..., [g4]], [z]] with one byte string per image in every inner list, "shape": hyper-latent
         (h, w), "down_ratio", "x_hat": the reconstruction :meth:`decompress` rebuilds, "size": the real bit count (8 x string
         bytes), "size_estimate": -log2 p of the coded symbols on the device}``.  The convolutions run on the pipeline of
         hip.BITSTREAM_HS_MODE whatever VC_FP32_MODE says: both compressors' entropy parameters depend on every stage in front
-        of them, so the whole pass decides how the strings are read."""
+        of them, so the whole pass decides how the strings are read.
+
+        ``coder="device"`` codes the same integers with the interleaved coder on the GPU: "strings" is then
+        ``{"offset": [payload per image], "residual": [...]}``, the result gains "coder" and "waves" (the wave count the decoder needs),
+        "size" is still 8 x the bytes of all payloads and x_hat is bit for bit that of the host-coded call."""
         _require_frames(xref1, xref2, xcur)
+        self._check_coder(coder, waves)
         s = self._coding_level(s)
         r1, r2, c = hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), hip.nchw_to_nhwc(xcur)
         if down_ratio is None:                 # (the choice travels in the stream: the search itself needs no pinning)
@@ -1131,17 +1190,38 @@ class FlowGuidedB(nn.Module):
         if down_ratio not in self.SEARCH_RATIOS:
             raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
         with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
-            out = self._bitstream_pass(r1, r2, scale1, scale2, c, s, down_ratio, trace=trace)
+            out = self._bitstream_pass(r1, r2, scale1, scale2, c, s, down_ratio, trace=trace, coder=coder, waves=waves)
             x_hat = hip.nhwc_to_nchw(out["x_hat"])
         strings = {k: out[k]["strings"] for k in ("offset", "residual")}
-        nbytes = sum(len(b) for k in strings for b in _flat_strings(strings[k]))
+        device = coder == "device"
+        nbytes = sum(len(b) for k in strings for b in (strings[k] if device else _flat_strings(strings[k])))
         estimate = float((out["offset"]["bits"] + out["residual"]["bits"]).item())
-        return {"strings": strings, "shape": out["offset"]["shape"], "down_ratio": down_ratio, "x_hat": x_hat, "size": 8 * nbytes,
-                "size_estimate": estimate}
+        result = {"strings": strings, "shape": out["offset"]["shape"], "down_ratio": down_ratio, "x_hat": x_hat, "size": 8 * nbytes,
+                  "size_estimate": estimate}
+        if device:
+            result.update({"coder": coder, "waves": int(waves)})
+        return result
 
-    def decompress(self, xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace=None):
-        """Decode the strings of :meth:`compress` from the two references alone: ``{"x_hat"}``."""
+    def upload_payloads(self, strings, waves=4):
+        """The payloads of ``compress(coder="device")`` on their way to the device (pinned, non-blocking) and their sub-stream
+        headers read there: ``{"offset", "residual"}`` of hip.IransDecoder.  :meth:`decompress` takes the result in place of the
+        strings; the caller then owns the one look at the error words, ``finish()`` of both, after it has used x_hat."""
+        self._check_coder("device", waves)
+        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"} or len(strings["offset"]) != len(strings["residual"]) \
+                or not all(isinstance(b, (bytes, bytearray)) for k in strings for b in strings[k]) or not strings["offset"]:
+            raise hip.VcError('strings: {"offset": [payload per image], "residual": [payload per image]}')
+        dev = self.offset_compressor.Gain.device
+        return {k: hip.IransDecoder(strings[k], waves, dev) for k in ("offset", "residual")}
+
+    def decompress(self, xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace=None, coder="host", waves=4):
+        """Decode the strings of :meth:`compress` from the two references alone: ``{"x_hat"}``.  ``coder="device"`` reads the
+        payloads of ``compress(coder="device")`` (``waves`` as it returned it): one upload, then launches only -- no copy to the
+        host and no synchronisation until x_hat is enqueued -- and one read of the decoders' error words at the end (VcError).
+        ``strings`` may be the result of :meth:`upload_payloads`; that last read is then the caller's."""
         _require_frames(xref1, xref2)
+        self._check_coder(coder, waves)
+        if coder == "device":
+            return self._decompress_device(xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace, waves)
         s = self._coding_level(s)
         down_ratio = int(down_ratio)
         if down_ratio not in self.SEARCH_RATIOS:
@@ -1156,6 +1236,28 @@ class FlowGuidedB(nn.Module):
             out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), scale1, scale2, None, s, down_ratio,
                                        strings=strings, shape=(hz, wz), trace=trace)
             return {"x_hat": hip.nhwc_to_nchw(out["x_hat"])}
+
+    def _decompress_device(self, xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace, waves):
+        s = self._coding_level(s)
+        down_ratio = int(down_ratio)
+        if down_ratio not in self.SEARCH_RATIOS:
+            raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
+        uploaded = isinstance(strings, dict) and all(isinstance(v, hip.IransDecoder) for v in strings.values())
+        decoders = strings if uploaded else self.upload_payloads(strings, waves)
+        if set(decoders) != {"offset", "residual"}:
+            raise hip.VcError('strings: {"offset": ..., "residual": ...}')
+        hz, wz = int(shape[0]), int(shape[1])
+        if (64 * hz, 64 * wz) != tuple(xref1.shape[2:]) or any(d.images != xref1.shape[0] or d.waves != int(waves) for d in decoders.values()):
+            raise hip.VcError(f"hyper-latent shape {hz}x{wz} / {decoders['offset'].images} image(s) / waves {waves} do not belong to "
+                              f"references {tuple(xref1.shape)} and the uploaded payloads")
+        with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
+            out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), scale1, scale2, None, s, down_ratio,
+                                       strings=decoders, shape=(hz, wz), trace=trace)
+            x_hat = hip.nhwc_to_nchw(out["x_hat"])
+        if not uploaded:
+            for d in decoders.values():
+                d.finish()
+        return {"x_hat": x_hat}
 
     # -- motion-adaptive flow resolution (opt_helpers.py:23-51) --------------------------------------------
     def _predict_from_flow(self, flow, xref1, xref2, s1, s2):

@@ -382,6 +382,22 @@ class EntropyModel(_Prepared):
         self.register_buffer("_offset", torch.IntTensor())
         self.register_buffer("_quantized_cdf", torch.IntTensor())
         self.register_buffer("_cdf_length", torch.IntTensor())
+        self._irans = None
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._irans = None
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *a, **k):
+        self._irans = None
+        return super()._apply(fn, *a, **k)
+
+    def irans_tables(self):
+        """the tables packed for the interleaved coder's kernels, resident on the model's device (hip.IransTables); built on first
+        use, dropped by update() and whenever the buffers are loaded or moved"""
+        if self._irans is None:
+            self._irans = hip.IransTables(*self.tables(), self._quantized_cdf.device)
+        return self._irans
 
     def _pmf_to_cdf(self, pmf, tail_mass, pmf_length, max_length):
         cdf = torch.zeros((len(pmf_length), max_length + 2), dtype=torch.int32)
@@ -451,6 +467,7 @@ class EntropyBottleneck(EntropyModel):
         self._quantized_cdf = self._pmf_to_cdf(pmf, tail_mass, pmf_length, max_length).to(dev)
         self._cdf_length = (pmf_length + 2).int().to(dev)
         self._offset = (-minima).int().to(dev)
+        self._irans = None
         return True
 
     def device_params(self):
@@ -508,6 +525,7 @@ class GaussianConditional(EntropyModel):
         self._offset = (-pmf_center).int().to(dev)
         self._cdf_length = (pmf_length + 2).int().to(dev)
         self._packed = None
+        self._irans = None
 
 
 def get_scale_table(lo=0.11, hi=256, levels=64):
