@@ -244,7 +244,7 @@ int vc_spynet_preprocess(vc_stream s, const float *src_nchw, vc_view dst);
 int vc_spynet_level_input(vc_stream s, vc_view first, vc_view second, vc_view flow_coarse,
                           vc_view feat8, vc_view up2);
 /* The same with the 8-channel level input written as a dense split tensor (one 48-byte record per pixel, see VC_CFG_SPLIT): the
- * first 7x7 layer then reads it as it lies. */
+ * first 7x7 layer then reads it as it lies.  The record is bit for bit vc_split3 of what vc_spynet_level_input writes. */
 int vc_spynet_level_input_sp3(vc_stream s, vc_view first, vc_view second, vc_view flow_coarse, void *feat_split, vc_view up);
 
 /* LHBDC mask blend + residual (m.py:63-67): pred = m*fw + (1-m)*bw ; resid = cur - pred.

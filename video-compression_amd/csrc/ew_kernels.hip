@@ -171,6 +171,9 @@ template <bool OSP, bool ROWS> __global__ void k_avgpool2_sp3(const unsigned cha
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
+            // (contraction off: vc_split3's `x - hi` would fuse with the product by `scale` and take the UNROUNDED product apart -- the
+            //  split result then differed from the fp32 result in the last bit for every scale that is no power of two)
+#pragma clang fp contract(off)
             float sum = 0.0f;
             sum += a0[e]; sum += a1[e]; sum += a2[e]; sum += a3[e];
             v[e] = sum * 0.25f * scale;
@@ -632,6 +635,11 @@ __device__ __forceinline__ float grid_coord(int convention, int i, float d, int 
     return 2.0f * (x / (float)size_img - 0.5f);
 }
 
+// PIN: the weighted sum as ONE stated chain of fused multiply-adds instead of an expression the compiler contracts as it likes.  The
+// level-input kernels sample three channels per thread, and the compiler paired them into packed fp32 instructions differently in each
+// instantiation: the third channel came out as `(nw A + ne B) + fma..` in the fp32 form and as `fma.. + (se D)` in the split form, one
+// ulp apart at 4-19 % of the pixels.  The chain below is what the first two channels were in every form.
+template <bool PIN = false>
 __device__ __forceinline__ float sample_bilinear(const float *img, long long sh, long long sw, int H, int W,
                                                  float gx, float gy, bool border, bool align_corners = false)
 {
@@ -655,6 +663,10 @@ __device__ __forceinline__ float sample_bilinear(const float *img, long long sh,
     const float ne = (x1ok && y0ok) ? img[(long long)y0 * sh + (long long)x1 * sw] : 0.0f;
     const float sw_ = (x0ok && y1ok) ? img[(long long)y1 * sh + (long long)x0 * sw] : 0.0f;
     const float se = (x1ok && y1ok) ? img[(long long)y1 * sh + (long long)x1 * sw] : 0.0f;
+    if (PIN) {
+        const float t = ne * (s_ * w);       // (rounded: it enters the chain as an addend, nothing can fuse with it)
+        return __builtin_fmaf(se, n * w, __builtin_fmaf(sw_, n * e, __builtin_fmaf(nw, s_ * e, t)));
+    }
     return nw * (s_ * e) + ne * (s_ * w) + sw_ * (n * e) + se * (n * w);
 }
 
@@ -854,9 +866,9 @@ template <bool VEC, bool SP3 = false> __global__ void k_spynet_level_input(vc_vi
         const float *f1 = first.p + view_off(first, n, y, x);
         const float *s2 = second.p + (long long)n * second.sn;
         float *o = feat.p + view_off(feat, n, y, x);
-        const float w0 = sample_bilinear(s2 + 0, second.sh, second.sw, second.h, second.w, gx, gy, true);
-        const float w1 = sample_bilinear(s2 + 1, second.sh, second.sw, second.h, second.w, gx, gy, true);
-        const float w2 = sample_bilinear(s2 + 2, second.sh, second.sw, second.h, second.w, gx, gy, true);
+        const float w0 = sample_bilinear<true>(s2 + 0, second.sh, second.sw, second.h, second.w, gx, gy, true);
+        const float w1 = sample_bilinear<true>(s2 + 1, second.sh, second.sw, second.h, second.w, gx, gy, true);
+        const float w2 = sample_bilinear<true>(s2 + 2, second.sh, second.sw, second.h, second.w, gx, gy, true);
         float *q = up.p + view_off(up, n, y, x);
         if (SP3) {
             const f32x4 lo = {f1[0], f1[1], f1[2], w0}, hi = {w1, w2, u, v};
@@ -1059,9 +1071,9 @@ template <bool SP3, int VAR> __global__ void k_spynet_level_input_3d(vc_view fir
         const float *f1 = first.p + view_off(first, n, y, x);
         const float *s2 = second.p + (long long)n * second.sn;
         float *o = feat.p + view_off(feat, n, y, x);
-        const float w0 = sample_bilinear(s2 + 0, second.sh, second.sw, second.h, second.w, gx, gy, true);
-        const float w1 = sample_bilinear(s2 + 1, second.sh, second.sw, second.h, second.w, gx, gy, true);
-        const float w2 = sample_bilinear(s2 + 2, second.sh, second.sw, second.h, second.w, gx, gy, true);
+        const float w0 = sample_bilinear<true>(s2 + 0, second.sh, second.sw, second.h, second.w, gx, gy, true);
+        const float w1 = sample_bilinear<true>(s2 + 1, second.sh, second.sw, second.h, second.w, gx, gy, true);
+        const float w2 = sample_bilinear<true>(s2 + 2, second.sh, second.sw, second.h, second.w, gx, gy, true);
         float *q = up.p + view_off(up, n, y, x);
         const f32x4 lo = {f1[0], f1[1], f1[2], w0}, hi = {w1, w2, u, v};
         const f32x2 uv = {u, v};
