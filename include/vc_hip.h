@@ -540,6 +540,26 @@ int vc_irans_decode_begin(vc_stream s, const uint32_t *payloads, size_t payload_
                           vc_irans_dstate *states);
 int vc_irans_decode(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, const int32_t *indexes,
                     size_t count, vc_irans_dtables tables, int32_t *symbols_out);
+/* Fused forms of vc_irans_decode for the two segments of a mean-scale hyperprior payload (the LHBDC stream codec's
+ * coder="device"; additive to ABI 6).  Same launch shape, same state struct, same round loop and the same
+ * guarantee; neither reads an index tensor nor leaves a symbol tensor behind.  Symbol i of an image is element (c, y, x) of the
+ * NCHW raster of the [images, h, w, c] NHWC view that is written, i = (c * h + y) * w + x; count must equal c * h * w.
+ *   _eb: table index = c (checked against n_tables like any index); z_hat[n, y, x, c] = what vc_eb_dequant writes for the decoded
+ *        integer (symbol + median of channel c, times out_gain[c] when out_gain is given).
+ *   _gc: table index = the one vc_gc_indexes derives from scales[n, y, x, c] (lower bound 0.11, then the count over scale_table,
+ *        n_scales in 2 .. 64: the table is kept in LDS); y_hat[n, y, x, c] = what vc_gc_dequant writes (symbol + means[n, y, x, c],
+ *        times out_gain[c]).
+ * Both share those expressions with the unfused kernels (csrc/entropy_shared.h): the outputs are bit-identical to the chain
+ * index tensor -> vc_irans_decode -> de-quantisation.  A wave that has met a violation writes the de-quantisation of 0.  The
+ * views may be channel or plane windows of larger tensors.  symbols_out (nullable; dense [images][count]) receives the
+ * integers, for tests and traces.  VC_EINVAL before any launch: null pointers, sizes < 1, a view whose n is not `images`,
+ * count != c * h * w, scales / means of another shape than y_hat.  vc_irans_tables_in_lds holds for both (the Gaussian form opts
+ * in to the 256 bytes its scale table takes past 64 KiB for the largest staged sets). */
+int vc_irans_decode_eb(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
+                       vc_irans_dtables tables, const float *eb_params, const float *out_gain, vc_view z_hat, int32_t *symbols_out);
+int vc_irans_decode_gc(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
+                       vc_irans_dtables tables, vc_view scales, vc_view means, const float *scale_table, int n_scales,
+                       const float *out_gain, vc_view y_hat, int32_t *symbols_out);
 
 /* ------------------------------------------------------------------------------------------
  * Entry points under the operator names SURVEY.md section 8(b) lists for the boundary.  Thin forwards to the

@@ -11,6 +11,7 @@
 // coder consumes (CompressAI flattens NCHW tensors).
 #include "common.h"
 #include "ew_rowmap.h"
+#include "entropy_shared.h"
 
 #define ENT_BLOCK 256
 #define ENT_SLOTS 1024
@@ -119,8 +120,7 @@ __global__ void k_eb_dequant(const int32_t *__restrict__ symbols, const float *_
         const int y = (int)(t % zh.h);
         const int n = (int)(t / zh.h);
         const float med = params[(long long)c * VC_EB_PARAMS_PER_CHANNEL + 58];
-        const float v = (float)symbols[(((long long)n * zh.c + c) * zh.h + y) * zh.w + x] + med;
-        zh.p[view_off(zh, n, y, x) + c] = out_gain ? v * out_gain[c] : v;
+        zh.p[view_off(zh, n, y, x) + c] = vc_eb_dequant_value(symbols[(((long long)n * zh.c + c) * zh.h + y) * zh.w + x], med, out_gain, c);
     }
 }
 
@@ -131,14 +131,6 @@ extern "C" int vc_eb_dequant(vc_stream s, const int32_t *symbols, const float *p
     hipLaunchKernelGGL(k_eb_dequant, dim3(ew_grid(total, ENT_BLOCK)), dim3(ENT_BLOCK), 0, as_stream(s), symbols, params, out_gain, z_hat);
     VC_LAUNCH_CHECK();
     return VC_OK;
-}
-
-__device__ __forceinline__ int scale_index(float s, const float *__restrict__ table, int n_scales)
-{
-    // build_indexes: (n_scales-1) - #{t in table[:-1] : s <= t}; table is ascending, so count from the top
-    int idx = n_scales - 1;
-    for (int k = 0; k < n_scales - 1; ++k) idx -= (s <= table[k]) ? 1 : 0;
-    return idx;
 }
 
 __global__ void __launch_bounds__(ENT_BLOCK) k_gc_forward(vc_view yv, vc_view sc, vc_view mu, const float *__restrict__ in_gain,
@@ -163,7 +155,7 @@ __global__ void __launch_bounds__(ENT_BLOCK) k_gc_forward(vc_view yv, vc_view sc
         if (in_gain) v *= in_gain[c];
         const float m = mu.p[view_off(mu, n, y, x) + c];
         float s = sc.p[view_off(sc, n, y, x) + c];
-        s = fmaxf(s, 0.11f);                          // lower_bound_scale
+        s = vc_lower_bound_scale(s);
         const float q = rintf(v - m);
         const float yq = q + m;
         const float a = fabsf(yq - m);                // the reference subtracts the mean again
@@ -205,7 +197,7 @@ __global__ void k_gc_indexes(vc_view sc, const float *__restrict__ table, int n_
         const int x = (int)(t % sc.w); t /= sc.w;
         const int y = (int)(t % sc.h);
         const int n = (int)(t / sc.h);
-        const float s = fmaxf(sc.p[view_off(sc, n, y, x) + c], 0.11f);
+        const float s = vc_lower_bound_scale(sc.p[view_off(sc, n, y, x) + c]);
         indexes[(((long long)n * sc.c + c) * sc.h + y) * sc.w + x] = scale_index(s, table, n_scales);
     }
 }
@@ -228,8 +220,8 @@ __global__ void k_gc_dequant(const int32_t *__restrict__ symbols, vc_view mu, co
         const int x = (int)(t % yh.w); t /= yh.w;
         const int y = (int)(t % yh.h);
         const int n = (int)(t / yh.h);
-        const float v = (float)symbols[(((long long)n * yh.c + c) * yh.h + y) * yh.w + x] + mu.p[view_off(mu, n, y, x) + c];
-        yh.p[view_off(yh, n, y, x) + c] = out_gain ? v * out_gain[c] : v;
+        yh.p[view_off(yh, n, y, x) + c] =
+            vc_gc_dequant_value(symbols[(((long long)n * yh.c + c) * yh.h + y) * yh.w + x], mu.p[view_off(mu, n, y, x) + c], out_gain, c);
     }
 }
 
@@ -302,7 +294,7 @@ __global__ void __launch_bounds__(ENT_BLOCK) k_gc_forward_ckbd(vc_view yv, vc_vi
         if (in_gain) v *= in_gain[c];
         const float mv = mu.p[view_off(mu, n, y, x) + c];
         float s = sc.p[view_off(sc, n, y, x) + c];
-        s = fmaxf(s, 0.11f);                          // lower_bound_scale
+        s = vc_lower_bound_scale(s);
         const float q = rintf(v - mv);
         const float yq = q + mv;
         if (partial) {                                // the likelihood of k_gc_forward, term by term
@@ -346,7 +338,7 @@ __global__ void __launch_bounds__(ENT_BLOCK) k_gc_indexes_ckbd(vc_view sc, int p
     const int wh = sc.w >> 1;
     ew_for_each<ROWS>(m, sc.n, sc.h, wh, sc.c, [&](int n, int y, int xh, int c) {
         const int x = 2 * xh + ((y ^ parity) & 1);
-        const float s = fmaxf(sc.p[view_off(sc, n, y, x) + c], 0.11f);
+        const float s = vc_lower_bound_scale(sc.p[view_off(sc, n, y, x) + c]);
         indexes[(((long long)n * sc.c + c) * sc.h + y) * wh + xh] = scale_index(s, table, n_scales);
     });
 }
@@ -367,8 +359,8 @@ __global__ void __launch_bounds__(ENT_BLOCK) k_gc_dequant_ckbd(const int32_t *__
     const int wh = yh.w >> 1;
     ew_for_each<ROWS>(m, yh.n, yh.h, wh, yh.c, [&](int n, int y, int xh, int c) {
         const int x = 2 * xh + ((y ^ parity) & 1);
-        const float v = (float)symbols[(((long long)n * yh.c + c) * yh.h + y) * wh + xh] + mu.p[view_off(mu, n, y, x) + c];
-        yh.p[view_off(yh, n, y, x) + c] = out_gain ? v * out_gain[c] : v;
+        yh.p[view_off(yh, n, y, x) + c] =
+            vc_gc_dequant_value(symbols[(((long long)n * yh.c + c) * yh.h + y) * wh + xh], mu.p[view_off(mu, n, y, x) + c], out_gain, c);
     });
 }
 

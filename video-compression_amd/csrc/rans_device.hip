@@ -10,15 +10,21 @@
 // the sub-stream's count (checked against the uploaded length by vc_irans_decode_begin), the search stays inside the row;
 // a violation sets the wave's error word (and the image's sticky one, for the host): the wave decodes zeros from there on, every
 // wave of the image from the next launch on -- a wave looks at its siblings' words only as earlier launches left them, so the
-// zeros do not depend on which wave runs first.
+// zeros do not depend on which wave runs first.  The fused forms (vc_irans_decode_eb / vc_irans_decode_gc: the LHBDC stream codec,
+// DESIGN.md section 4e) run the same round loop, take the table index from the channel / the scale and write the de-quantised
+// latent; behind a violation they write the de-quantisation of 0.  vc_irans_tables_in_lds describes all three: the Gaussian form
+// keeps its scale table (64 floats) behind the cdf rows and, for the sets between 64 KiB - 256 bytes and 64 KiB, asks for the
+// 256 bytes past 64 KiB by opting in, so the boundary between the staged and the global form does not move.
 //
 // Encoder: one launch per payload, walking segments, rounds and sub-steps backwards; tables read from global memory and a
 // plain 64-by-32-bit division per step (not on any critical path: the encoder waits for the networks, not they for it).
 #include "common.h"
 #include "rans_lanes.h"
+#include "entropy_shared.h"
 
 namespace {
 constexpr int kLdsTableBytes = 64 * 1024;
+constexpr int kScaleSlots = 64;                // floats of LDS the fused Gaussian form keeps its scale table in
 
 struct EncArgs {
     vc_irans_dsegment segs[VC_IRANS_MAX_SEGMENTS];
@@ -136,11 +142,93 @@ __global__ __launch_bounds__(64) void irans_begin_kernel(const uint32_t *payload
     }
 }
 
-template <bool kLds>
-__global__ __launch_bounds__(64) void irans_decode_kernel(const uint32_t *payloads, vc_irans_dstate *states, int waves, const int32_t *indexes,
-                                                          uint32_t count, const vc_irans_dtables tab, int32_t *out)
+// ------------------------------------------------------------------------------------------------------------------------------
+// Decoder.  ONE round loop (irans_decode_segment) for the three entry points; what differs between them is where a symbol's table
+// index comes from and where the decoded integer goes -- an `Io`:
+//     Item fetch(image, i)                 everything symbol i needs that does NOT depend on the coder state: its table index and
+//                                          whatever the store wants later (a median, a mean, the position)
+//     void store(image, i, item, symbol)   the decoded integer (0 behind a violation) to its destination
+// PlainIo: index tensor in, integer tensor out (vc_irans_decode).  EbIo: the index is the channel i / (h w), the store writes
+// z_hat as vc_eb_dequant would (vc_irans_decode_eb).  GcIo: the index is scale_index of the NHWC scale, the store writes y_hat as
+// vc_gc_dequant would (vc_irans_decode_gc); both through the expressions of entropy_shared.h that entropy.hip itself uses.
+// fetch() for round r + 1 is issued before the state chain of round r (state -> cumulative value -> search -> state -> words), so
+// its loads (and the 63 compares of scale_index) are in flight while that chain is waited on.
+// ------------------------------------------------------------------------------------------------------------------------------
+struct PlainIo {
+    struct Item { int32_t index; };
+    const int32_t *indexes;
+    int32_t *out;
+    uint32_t count;
+    __device__ __forceinline__ Item fetch(int image, uint32_t i) const { return {indexes[static_cast<size_t>(image) * count + i]}; }
+    __device__ __forceinline__ void store(int image, uint32_t i, const Item &, int32_t symbol) const
+    {
+        out[static_cast<size_t>(image) * count + i] = symbol;
+    }
+};
+
+// symbol i of an image = element (c, y, x) of its NCHW raster
+struct Raster {
+    uint32_t hw, w;
+    __device__ __forceinline__ void split(uint32_t i, int &c, int &y, int &x) const
+    {
+        const uint32_t cc = i / hw, rem = i - cc * hw, yy = rem / w;
+        c = static_cast<int>(cc);
+        y = static_cast<int>(yy);
+        x = static_cast<int>(rem - yy * w);
+    }
+};
+
+struct EbIo {
+    struct Item { int32_t index; float med; int y, x; };
+    Raster ras;
+    const float *params, *out_gain;
+    vc_view zh;
+    int32_t *symbols;                          // nullable: dense [images][count]
+    uint32_t count;
+    __device__ __forceinline__ Item fetch(int, uint32_t i) const
+    {
+        Item it;
+        ras.split(i, it.index, it.y, it.x);    // the table of a hyper-latent is its channel's
+        it.med = params[static_cast<long long>(it.index) * VC_EB_PARAMS_PER_CHANNEL + 58];
+        return it;
+    }
+    __device__ __forceinline__ void store(int image, uint32_t i, const Item &it, int32_t symbol) const
+    {
+        zh.p[view_off(zh, image, it.y, it.x) + it.index] = vc_eb_dequant_value(symbol, it.med, out_gain, it.index);
+        if (symbols) symbols[static_cast<size_t>(image) * count + i] = symbol;
+    }
+};
+
+struct GcIo {
+    struct Item { int32_t index; float mean; int c, y, x; };
+    Raster ras;
+    vc_view sc, mu, yh;
+    const float *table;                        // the scale table, staged in LDS by the kernel
+    int n_scales;
+    const float *out_gain;
+    int32_t *symbols;                          // nullable: dense [images][count]
+    uint32_t count;
+    __device__ __forceinline__ Item fetch(int image, uint32_t i) const
+    {
+        Item it;
+        ras.split(i, it.c, it.y, it.x);
+        it.index = scale_index(vc_lower_bound_scale(sc.p[view_off(sc, image, it.y, it.x) + it.c]), table, n_scales);
+        it.mean = mu.p[view_off(mu, image, it.y, it.x) + it.c];
+        return it;
+    }
+    __device__ __forceinline__ void store(int image, uint32_t i, const Item &it, int32_t symbol) const
+    {
+        yh.p[view_off(yh, image, it.y, it.x) + it.c] = vc_gc_dequant_value(symbol, it.mean, out_gain, it.c);
+        if (symbols) symbols[static_cast<size_t>(image) * count + i] = symbol;
+    }
+};
+
+// One segment of one (image, wave): `staged` = the workgroup's LDS for the cdf rows (kLds) -- whatever else a kernel keeps in LDS it
+// has written AND synchronised before it calls this.
+template <bool kLds, class Io>
+__device__ __forceinline__ void irans_decode_segment(const uint32_t *payloads, vc_irans_dstate *states, int waves, uint32_t count,
+                                                     const vc_irans_dtables &tab, uint16_t *staged, const Io &io)
 {
-    extern __shared__ __attribute__((aligned(16))) uint16_t staged[];
     const int lane = threadIdx.x, image = blockIdx.x / waves, wave = blockIdx.x % waves;
     const uint16_t *cdf16 = tab.cdf16;
     if (kLds) {                                // entries is a multiple of 8: whole 16-byte chunks
@@ -162,8 +250,6 @@ __global__ __launch_bounds__(64) void irans_decode_kernel(const uint32_t *payloa
         dead |= e != 0 && (e >> 3) <= launch;
     }
     uint32_t err = 0;
-    const int32_t *idx = indexes + static_cast<size_t>(image) * count;
-    int32_t *dst = out + static_cast<size_t>(image) * count;
     const uint32_t lanes = irl::kLanes * waves;
     const uint32_t rounds = count / lanes + (count % lanes != 0);
 
@@ -179,15 +265,19 @@ __global__ __launch_bounds__(64) void irans_decode_kernel(const uint32_t *payloa
         return true;
     };
 
-    for (uint32_t r = 0; r < rounds; ++r) {
-        const uint32_t i = r * lanes + wave * irl::kLanes + lane;
+    uint32_t i = wave * irl::kLanes + lane;    // (count < 2^31, lanes <= 1024: i + lanes cannot wrap)
+    typename Io::Item next = {};
+    if (i < count) next = io.fetch(image, i);
+    for (uint32_t r = 0; r < rounds; ++r, i += lanes) {
         const bool active = i < count;
+        const typename Io::Item cur = next;
+        if (i + lanes < count) next = io.fetch(image, i + lanes);  // round r + 1: nothing in it depends on x
         int32_t symbol = 0;
         if (!dead) {
             bool escaped = false, bad_index = false;
             irl::Row row = {0, 3, 0, 0};
             if (active) {
-                const int32_t t = idx[i];
+                const int32_t t = cur.index;
                 bad_index = static_cast<uint32_t>(t) >= static_cast<uint32_t>(tab.n_tables);
                 if (!bad_index) {
                     row = row_of(tab, t);
@@ -226,7 +316,7 @@ __global__ __launch_bounds__(64) void irans_decode_kernel(const uint32_t *payloa
                 }
             }
         }
-        if (active) dst[i] = dead ? 0 : symbol;
+        if (active) io.store(image, i, cur, dead ? 0 : symbol);
     }
     st->x[wave][lane] = x;
     if (lane == 0) {
@@ -237,6 +327,34 @@ __global__ __launch_bounds__(64) void irans_decode_kernel(const uint32_t *payloa
             atomicOr(&st->error, err);
         }
     }
+}
+
+extern __shared__ __attribute__((aligned(16))) uint16_t irans_lds[];
+
+template <bool kLds>
+__global__ __launch_bounds__(64) void irans_decode_kernel(const uint32_t *payloads, vc_irans_dstate *states, int waves, const int32_t *indexes,
+                                                          uint32_t count, const vc_irans_dtables tab, int32_t *out)
+{
+    irans_decode_segment<kLds>(payloads, states, waves, count, tab, irans_lds, PlainIo{indexes, out, count});
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(64) void irans_decode_eb_kernel(const uint32_t *payloads, vc_irans_dstate *states, int waves, uint32_t count,
+                                                             const vc_irans_dtables tab, const EbIo io)
+{
+    irans_decode_segment<kLds>(payloads, states, waves, count, tab, irans_lds, io);
+}
+
+// LDS: the cdf rows (kLds; 2 * entries bytes, a multiple of 16), then the kScaleSlots floats of the scale table
+template <bool kLds>
+__global__ __launch_bounds__(64) void irans_decode_gc_kernel(const uint32_t *payloads, vc_irans_dstate *states, int waves, uint32_t count,
+                                                             const vc_irans_dtables tab, GcIo io)
+{
+    float *table = reinterpret_cast<float *>(irans_lds + (kLds ? tab.entries : 0));
+    if (static_cast<int>(threadIdx.x) < io.n_scales) table[threadIdx.x] = io.table[threadIdx.x];      // n_scales <= kScaleSlots = 64 lanes
+    __syncthreads();
+    io.table = table;
+    irans_decode_segment<kLds>(payloads, states, waves, count, tab, irans_lds, io);
 }
 
 bool dtables_ok(const vc_irans_dtables &t)
@@ -302,6 +420,65 @@ extern "C" int vc_irans_decode(vc_stream s, const uint32_t *payloads, vc_irans_d
     else
         hipLaunchKernelGGL(irans_decode_kernel<false>, grid, block, 0, as_stream(s), payloads, states, waves, indexes,
                            static_cast<uint32_t>(count), tables, symbols_out);
+    VC_LAUNCH_CHECK();
+    return VC_OK;
+}
+
+namespace {
+bool fused_view_ok(const vc_view &v, int images) { return v.p && v.n == images && v.h >= 1 && v.w >= 1 && v.c >= 1; }
+bool same_shape(const vc_view &a, const vc_view &b) { return a.n == b.n && a.h == b.h && a.w == b.w && a.c == b.c; }
+// count == c * h * w, below 2^31
+bool fused_count_ok(const vc_view &v, size_t count)
+{
+    const unsigned long long hw = static_cast<unsigned long long>(v.h) * static_cast<unsigned long long>(v.w);
+    return hw <= 0x7fffffffull && hw * static_cast<unsigned long long>(v.c) <= 0x7fffffffull && count == hw * static_cast<unsigned long long>(v.c);
+}
+bool fused_common_ok(const uint32_t *payloads, const vc_irans_dstate *states, int images, int waves, const vc_irans_dtables &tables)
+{
+    return payloads && states && images >= 1 && images <= (1 << 20) && irl::waves_ok(waves) && dtables_ok(tables);
+}
+}  // namespace
+
+extern "C" int vc_irans_decode_eb(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
+                                  vc_irans_dtables tables, const float *eb_params, const float *out_gain, vc_view z_hat, int32_t *symbols_out)
+{
+    if (!fused_common_ok(payloads, states, images, waves, tables) || !eb_params || !fused_view_ok(z_hat, images) || !fused_count_ok(z_hat, count))
+        return VC_EINVAL;
+    const EbIo io = {{static_cast<uint32_t>(z_hat.h) * static_cast<uint32_t>(z_hat.w), static_cast<uint32_t>(z_hat.w)}, eb_params, out_gain, z_hat,
+                     symbols_out, static_cast<uint32_t>(count)};
+    const dim3 grid(images * waves), block(irl::kLanes);
+    if (vc_irans_tables_in_lds(tables.entries))
+        hipLaunchKernelGGL(irans_decode_eb_kernel<true>, grid, block, 2 * static_cast<size_t>(tables.entries), as_stream(s), payloads, states,
+                           waves, static_cast<uint32_t>(count), tables, io);
+    else
+        hipLaunchKernelGGL(irans_decode_eb_kernel<false>, grid, block, 0, as_stream(s), payloads, states, waves, static_cast<uint32_t>(count),
+                           tables, io);
+    VC_LAUNCH_CHECK();
+    return VC_OK;
+}
+
+extern "C" int vc_irans_decode_gc(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
+                                  vc_irans_dtables tables, vc_view scales, vc_view means, const float *scale_table, int n_scales,
+                                  const float *out_gain, vc_view y_hat, int32_t *symbols_out)
+{
+    if (!fused_common_ok(payloads, states, images, waves, tables) || !scale_table || n_scales < 2 || n_scales > kScaleSlots ||
+        !fused_view_ok(y_hat, images) || !fused_view_ok(scales, images) || !fused_view_ok(means, images) || !same_shape(scales, y_hat) ||
+        !same_shape(means, y_hat) || !fused_count_ok(y_hat, count))
+        return VC_EINVAL;
+    const GcIo io = {{static_cast<uint32_t>(y_hat.h) * static_cast<uint32_t>(y_hat.w), static_cast<uint32_t>(y_hat.w)}, scales, means, y_hat,
+                     scale_table, n_scales, out_gain, symbols_out, static_cast<uint32_t>(count)};
+    const dim3 grid(images * waves), block(irl::kLanes);
+    constexpr size_t table_bytes = kScaleSlots * sizeof(float);
+    if (vc_irans_tables_in_lds(tables.entries)) {
+        static vc_lds_raised raised;           // (only the sets within 256 bytes of 64 KiB get here past the default limit)
+        const size_t lds = 2 * static_cast<size_t>(tables.entries) + table_bytes;
+        if (!vc_raise_lds_limit(reinterpret_cast<const void *>(&irans_decode_gc_kernel<true>), lds, raised)) return VC_ELAUNCH;
+        hipLaunchKernelGGL(irans_decode_gc_kernel<true>, grid, block, lds, as_stream(s), payloads, states, waves, static_cast<uint32_t>(count),
+                           tables, io);
+    } else {
+        hipLaunchKernelGGL(irans_decode_gc_kernel<false>, grid, block, table_bytes, as_stream(s), payloads, states, waves,
+                           static_cast<uint32_t>(count), tables, io);
+    }
     VC_LAUNCH_CHECK();
     return VC_OK;
 }

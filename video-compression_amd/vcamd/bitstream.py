@@ -17,6 +17,11 @@ Wiring = the CLI's (both flow predictors equal pad(flow_ab): SURVEY.md Appendix 
 the reference's decode_B.py and vice versa.  The encoder-side reconstruction equals the decoder's output bit for bit
 (same integers, same kernels) -- asserted in tests/test_stream_gpu.py.
 
+``LhbdcStreamCodec(coder="device")`` (opt-in) keeps the entropy coding on the GPU instead: the same integers in
+``VCLD`` containers of the project's own interleaved coder, one ``vc_irans_encode`` launch per compressor on the encoder and two fused
+decode kernels per compressor on the decoder (``vc_irans_decode_eb`` / ``vc_irans_decode_gc``: no index tensor, no symbol tensor),
+so a GOP decodes as uploads, then launches only, then one read of the error words.
+
 Flex-Rate is not offered here on purpose: its compress() codes the UN-gained latent while forward() quantises the gained
 one (quirk B.6), so the reference's own encoder and decoder disagree on the reconstruction whenever the gain differs from
 one -- there is no closed loop to pipeline.
@@ -66,9 +71,18 @@ class PendingContainers:
 
 
 class LhbdcStreamCodec:
-    def __init__(self, model: Model, lmbda=1626, workers=4):
+    """``coder="host"`` (default): bits_B.bin containers, the host range coder on worker threads, as described above.
+    ``coder="device"``: VCLD containers (below) coded and decoded by the interleaved range coder's kernels -- the same integers,
+    the same reconstructions; ``waves`` sub-streams per payload on the encoder (the decoder takes the count from the container).
+    The worker pool is not created: nothing is coded on the host."""
+    CODERS = ("host", "device")
+
+    def __init__(self, model: Model, lmbda=1626, workers=4, coder="host", waves=4):
+        if coder not in self.CODERS or not hip.irans_waves_ok(waves):
+            raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {self.CODERS}, waves a power of two in 1..16")
         self.model, self.lmbda = model, int(lmbda)
-        self.pool = ThreadPoolExecutor(max_workers=workers)
+        self.coder, self.waves = coder, int(waves)
+        self.pool = ThreadPoolExecutor(max_workers=workers) if coder == "host" else None
         self.copy_stream = None
         self.t_mv = _Tables(model.mv_compressor)
         self.t_res = _Tables(model.residual_compressor)
@@ -96,6 +110,8 @@ class LhbdcStreamCodec:
     def encode_frames(self, x_before, x_current, x_after):
         """n independent B-frames (one hierarchy level).  Returns (x_hat NCHW = what decode_frames will output,
         PendingContainers).  No host synchronisation: the caller can enqueue the next level at once."""
+        if self.coder == "device":
+            return self._encode_frames_dev(x_before, x_current, x_after)
         m = self.model
         xb_, xc_, xa_ = (frame_list(t) for t in (x_before, x_current, x_after))      # tensors or lists of frames
         n, dev = _count(xc_), xc_[0].device
@@ -132,7 +148,15 @@ class LhbdcStreamCodec:
 
     # -- decoder ------------------------------------------------------------------------------------------
     def decode_frames(self, x_before, x_after, containers):
-        """n independent B-frames from their containers (bytes).  Returns x_hat NCHW [n,3,H,W]."""
+        """n independent B-frames from their containers (bytes).  Returns x_hat NCHW [n,3,H,W].  ``coder="device"``: upload,
+        launches only, then the one read of the decoders' error words (VcError, after x_hat is enqueued); an
+        :class:`UploadedLevel` in place of the containers skips the upload."""
+        if self.coder == "device":
+            level = containers if isinstance(containers, UploadedLevel) else self.upload_frames(containers, x_before)
+            x_hat = self._decode_level_dev(x_before, x_after, level)
+            level.finish()
+            return x_hat
+        _refuse_container_of_other_coder(containers, "host")
         m = self.model
         xb_, xa_ = frame_list(x_before), frame_list(x_after)
         n, dev = _count(xb_), xb_[0].device
@@ -169,6 +193,73 @@ class LhbdcStreamCodec:
         res_hat = m.residual_compressor.synth_decode_t(y_res, means_res)
         return hip.nhwc_to_nchw(hip.axpby(res_hat, pred))
 
+    # -- coder="device": the interleaved range coder's kernels on both sides -----------------
+    def _encode_frames_dev(self, x_before, x_current, x_after):
+        """encode_frames with the integers coded where they lie: per compressor one vc_irans_encode launch over two segments (z with
+        the factorised tables, y with the Gaussian ones) on the tensors of code_t.  Nothing is read back here: the one host
+        synchronisation of the level, the read of both compressors' word counts, happens in ``PendingDevContainers.result()``."""
+        m = self.model
+        xb_, xc_, xa_ = (frame_list(t) for t in (x_before, x_current, x_after))
+        n, dev = _count(xc_), xc_[0].device
+        frames = {"b": xb_, "c": xc_, "a": xa_}
+        flow_ba, flow_ab, hh, ww = _cli_predictors(m, frames, n)
+        cur = m._flows(frames, [("c", "b"), ("c", "a")])
+        cur_flows, _, _ = Model._pool_pad(cur, 1.0)
+        diff = T.empty(n, flow_ab.h, flow_ab.w, 4, dev)
+        hip.axpby(cur_flows.images(0, n), flow_ab, 1.0, -1.0, out=diff.channels(0, 2))
+        hip.axpby(cur_flows.images(n, 2 * n), flow_ba, 1.0, -1.0, out=diff.channels(2, 4))
+        mv_hat, mv_sym = m.mv_compressor.code_t(diff)
+        job_mv = self._encode_job(m.mv_compressor, mv_sym, n, dev)
+        xb, xc, xa = hip.nchw_frames_to_nhwc(xb_), hip.nchw_frames_to_nhwc(xc_), hip.nchw_frames_to_nhwc(xa_)
+        pred, resid = m._predict(xb, xa, mv_hat, flow_ab, flow_ba, hh, ww, cur=xc)
+        res_hat, res_sym = m.residual_compressor.code_t(resid)
+        job_res = self._encode_job(m.residual_compressor, res_sym, n, dev)
+        x_hat = hip.nhwc_to_nchw(hip.axpby(res_hat, pred))
+        return x_hat, PendingDevContainers([job_mv, job_res], self.lmbda, mv_sym["shape"], res_sym["shape"], self.waves, (mv_sym, res_sym))
+
+    def _encode_job(self, codec, sym, n, dev):
+        segments = [(sym["z_sym"], codec.z_index_dev(n, sym["shape"], dev), 0), (sym["y_sym"], sym["y_idx"], 1)]
+        return hip.irans_encode_launch(segments, [codec.entropy_bottleneck.irans_tables(), codec.gaussian_conditional.irans_tables()], self.waves)
+
+    def upload_frames(self, containers, like):
+        """The containers of n frames of one level on their way to the device: parsed and validated (VcError before anything is
+        allocated or launched), one hip.IransDecoder per compressor.  ``like``: a frame (or frames) of the sequence, for its size
+        and device."""
+        if self.coder != "device":
+            raise hip.VcError('upload_frames belongs to coder="device"')
+        like = frame_list(like)
+        h, w, dev = like[0].shape[-2], like[0].shape[-1], like[0].device
+        _refuse_container_of_other_coder(containers, "device")
+        parsed = [unpack_lhbdc_frame_dev(c, h, w) for c in containers]
+        if not parsed:
+            raise hip.VcError("one container per frame")
+        first = parsed[0]
+        if any((p["mv_shape"], p["res_shape"], p["waves"]) != (first["mv_shape"], first["res_shape"], first["waves"]) for p in parsed):
+            raise hip.VcError("frames of one pass must have the same latent shapes and wave count")
+        return UploadedLevel(hip.IransDecoder([p["mv"] for p in parsed], first["waves"], dev),
+                             hip.IransDecoder([p["res"] for p in parsed], first["waves"], dev), first["mv_shape"], first["res_shape"])
+
+    def upload_gop(self, containers, like):
+        """Every payload of a GOP ({order: container}) uploaded, level by level: what :meth:`decode_gop` then only launches on."""
+        return UploadedGop([self.upload_frames([containers[o] for o in group], like) for group in LEVEL_GROUPS])
+
+    def _decode_level_dev(self, x_before, x_after, level):
+        """Launches only: per compressor vc_irans_decode_eb -> hyper-synthesis -> vc_irans_decode_gc -> synthesis."""
+        m = self.model
+        xb_, xa_ = frame_list(x_before), frame_list(x_after)
+        n = _count(xb_)
+        if level.mv.images != n or level.res.images != n:
+            raise hip.VcError("one container per frame")
+        check_container_shapes(level.mv_shape, level.res_shape, xb_[0].shape[-2], xb_[0].shape[-1])
+        scales_mv, means_mv = m.mv_compressor.hyper_decode_dev_t(level.mv, level.mv_shape)
+        scales_res, means_res = m.residual_compressor.hyper_decode_dev_t(level.res, level.res_shape)
+        flow_ba, flow_ab, hh, ww = _cli_predictors(m, {"b": xb_, "a": xa_}, n)
+        xb, xa = hip.nchw_frames_to_nhwc(xb_), hip.nchw_frames_to_nhwc(xa_)
+        mv_hat = m.mv_compressor.synth_decode_dev_t(level.mv, scales_mv, means_mv)
+        pred, _ = m._predict(xb, xa, mv_hat, flow_ab, flow_ba, hh, ww)
+        res_hat = m.residual_compressor.synth_decode_dev_t(level.res, scales_res, means_res)
+        return hip.nhwc_to_nchw(hip.axpby(res_hat, pred))
+
     # -- GOP-8 in hierarchical order ------------------------------------------------------------------------
     def encode_gop(self, gop, dec_first, dec_last):
         """``gop``: 9 padded NCHW frames.  Returns ({order: container bytes}, {order: reconstruction}).  The host coding of
@@ -188,7 +279,24 @@ class LhbdcStreamCodec:
                 containers[o] = c
         return containers, decoded
 
-    def decode_gop(self, containers, dec_first, dec_last):
+    def decode_gop(self, containers, dec_first, dec_last, finish=True):
+        """``coder="device"``: every payload of the GOP is uploaded first (:meth:`upload_gop`; an :class:`UploadedGop` in place of
+        the containers skips that), the whole GOP is then enqueued as launches only, and ``finish`` reads every decoder's error
+        words once, after the last reconstruction has been enqueued: a corrupt container raises VcError THERE (the frames
+        behind the violation are decoded from zeros), never a fault.  ``finish=False`` leaves that read to the caller
+        (``UploadedGop.finish``)."""
+        if self.coder == "device":
+            up = containers if isinstance(containers, UploadedGop) else self.upload_gop(containers, dec_first)
+            decoded = {0: dec_first, 8: dec_last}
+            for group, level in zip(LEVEL_GROUPS, up.levels):
+                xb = [decoded[DECODING_INFO[o][0]] for o in group]
+                xa = [decoded[DECODING_INFO[o][1]] for o in group]
+                x_hat = self._decode_level_dev(xb, xa, level)
+                for i, o in enumerate(group):
+                    decoded[o] = x_hat[i:i + 1]
+            if finish:
+                up.finish()
+            return decoded
         decoded = {0: dec_first, 8: dec_last}
         for group in LEVEL_GROUPS:
             xb = [decoded[DECODING_INFO[o][0]] for o in group]
@@ -199,7 +307,125 @@ class LhbdcStreamCodec:
         return decoded
 
     def close(self):
-        self.pool.shutdown(wait=True)
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+
+
+# ------------------------------------------------------------------------------------------------
+# Device-coded LHBDC B-frame container (this project's own format; bits_B.bin stays the default and the reference's)
+# ------------------------------------------------------------------------------------------------
+# One byte string per coded frame, little-endian:
+#   offset  0  4 bytes  magic "VCLD"
+#           4  u8       version (1)
+#           5  u8       waves W (1, 2, 4, 8 or 16): sub-streams per payload
+#           6  u32      lambda (as bits_B.bin)
+#          10  u16 x 2  hyper-latent shape (h, w) of the motion compressor
+#          14  u16 x 2  hyper-latent shape (h, w) of the residual compressor
+#          18  u32 x 2  payload lengths: motion, residual
+#          26  the two payloads in that order
+# A payload is one interleaved-rANS payload (include/vc_hip.h: "Interleaved range coder") of two segments, states and cursors
+# continuing from the first to the second: the hyper-latent z (table set 0 = the factorised tables, index of symbol i =
+# i / (hz * wz), its channel), then the latent y (table set 1 = the Gaussian tables, index from the scales); symbol order = the int32
+# tensors of MeanScaleHyperprior.code_t (NCHW raster).
+LHBDC_DEV_MAGIC = b"VCLD"
+LHBDC_DEV_VERSION = 1
+LHBDC_DEV_HEADER = struct.Struct("<4sBBIHHHHII")
+_FORMATS = {"host": "bits_B.bin", "device": "VCLD"}
+
+
+def pack_lhbdc_frame_dev(lmbda, mv_shape, res_shape, waves, mv_payload, res_payload):
+    """The VCLD container of one frame from the two payloads of ``LhbdcStreamCodec(coder="device")``."""
+    shapes = tuple(int(v) for v in tuple(mv_shape) + tuple(res_shape))
+    if len(shapes) != 4 or not all(1 <= v <= 0xffff for v in shapes) or not hip.irans_waves_ok(waves) or not 0 <= int(lmbda) <= 0xffffffff:
+        raise hip.VcError(f"lambda {lmbda} / hyper-latent shapes {shapes} / waves {waves} do not fit the container")
+    mv_payload, res_payload = bytes(mv_payload), bytes(res_payload)
+    if max(len(mv_payload), len(res_payload)) > 0xffffffff:
+        raise hip.VcError("a payload is longer than the container's 32-bit length field")
+    return LHBDC_DEV_HEADER.pack(LHBDC_DEV_MAGIC, LHBDC_DEV_VERSION, int(waves), int(lmbda), *shapes, len(mv_payload),
+                                 len(res_payload)) + mv_payload + res_payload
+
+
+def unpack_lhbdc_frame_dev(data, h, w):
+    """Inverse of :func:`pack_lhbdc_frame_dev` for a (padded) h x w frame: ``{"lmbda", "waves", "mv_shape", "res_shape", "mv", "res"}``.
+    Magic, version, wave count, the lengths against the data (no trailing bytes, whole words, at least the W sub-stream headers)
+    and the shapes against the frame size (lhbdc.check_container_shapes) are validated before anything is returned, so before
+    anything is allocated from the header (VcError)."""
+    data = bytes(data)
+    if len(data) < LHBDC_DEV_HEADER.size:
+        raise hip.VcError(f"VCLD container: {len(data)} bytes is shorter than the {LHBDC_DEV_HEADER.size}-byte header")
+    magic, version, waves, lmbda, mh, mw, rh, rw, n_mv, n_res = LHBDC_DEV_HEADER.unpack_from(data, 0)
+    if magic != LHBDC_DEV_MAGIC:
+        raise hip.VcError(f"VCLD container: magic {magic!r} is not {LHBDC_DEV_MAGIC!r}")
+    if version != LHBDC_DEV_VERSION:
+        raise hip.VcError(f"VCLD container: version {version} (this reader knows {LHBDC_DEV_VERSION})")
+    if not hip.irans_waves_ok(waves):
+        raise hip.VcError(f"VCLD container: waves {waves} is not a power of two in 1..16")
+    fixed = LHBDC_DEV_HEADER.size
+    if fixed + n_mv + n_res != len(data) or min(n_mv, n_res) < waves * hip.IRANS_SUBSTREAM_HEADER or n_mv % 4 or n_res % 4:
+        raise hip.VcError(f"VCLD container: payload lengths {n_mv} + {n_res} do not fit {len(data)} bytes / {waves} waves")
+    check_container_shapes((mh, mw), (rh, rw), h, w)
+    return {"lmbda": lmbda, "waves": waves, "mv_shape": (mh, mw), "res_shape": (rh, rw), "mv": data[fixed:fixed + n_mv],
+            "res": data[fixed + n_mv:]}
+
+
+def _refuse_container_of_other_coder(containers, coder):
+    """A VCLD container handed to the host-coded path (or a bits_B.bin one to the device-coded path) would be parsed as the other
+    format's header: refuse it by name.  (The first field of bits_B.bin is lambda: "VCLD" there would be 1 145 848 662.)"""
+    if isinstance(containers, (UploadedLevel, UploadedGop)):
+        raise hip.VcError(f'uploaded {_FORMATS["device"]} payloads belong to coder="device", this codec reads {_FORMATS[coder]}')
+    for c in containers:
+        is_dev = bytes(c[:4]) == LHBDC_DEV_MAGIC
+        if is_dev != (coder == "device"):
+            other = "host" if coder == "device" else "device"
+            raise hip.VcError(f'this codec was built with coder="{coder}" and reads {_FORMATS[coder]} containers; this one '
+                              f'{"is" if is_dev else "is not"} a {_FORMATS["device"]} container (magic {bytes(c[:4])!r}): decode '
+                              f'{_FORMATS[other]} with coder="{other}"')
+
+
+class PendingDevContainers:
+    """Containers of one level coded on the device; ``result()`` does the level's one host synchronisation (the read of both
+    compressors' word counts), copies the used tails and packs the VCLD containers."""
+
+    def __init__(self, jobs, lmbda, mv_shape, res_shape, waves, keep_alive):
+        self._jobs, self._head, self._keep = jobs, (lmbda, mv_shape, res_shape, waves), keep_alive
+
+    def result(self):
+        mv, res = hip.irans_encode_collect(self._jobs)
+        self._keep = None
+        return [pack_lhbdc_frame_dev(*self._head, a, b) for a, b in zip(mv, res)]
+
+
+class UploadedLevel:
+    """The payloads of one level on the device: one hip.IransDecoder per compressor (one payload per frame each)."""
+
+    def __init__(self, mv, res, mv_shape, res_shape):
+        self.mv, self.res, self.mv_shape, self.res_shape = mv, res, tuple(mv_shape), tuple(res_shape)
+
+    def finish(self):
+        """the one read per decoder: VcError when a payload was corrupt (every decoder is read before the first error is raised)"""
+        errors = []
+        for d in (self.mv, self.res):
+            try:
+                d.finish()
+            except hip.VcError as e:
+                errors.append(e)
+        if errors:
+            raise errors[0]
+
+
+class UploadedGop:
+    def __init__(self, levels):
+        self.levels = levels
+
+    def finish(self):
+        errors = []
+        for level in self.levels:
+            try:
+                level.finish()
+            except hip.VcError as e:
+                errors.append(e)
+        if errors:
+            raise errors[0]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -235,6 +235,8 @@ def lib():
     sig("vc_irans_encode", ci, vp, vp, ci, vp, ci, ci, ci, vp, sz, vp)
     sig("vc_irans_decode_begin", ci, vp, vp, sz, vp, ci, ci, vp)
     sig("vc_irans_decode", ci, vp, vp, vp, ci, ci, vp, sz, IransDTables, vp)
+    sig("vc_irans_decode_eb", ci, vp, vp, vp, ci, ci, sz, IransDTables, vp, vp, View, vp)
+    sig("vc_irans_decode_gc", ci, vp, vp, vp, ci, ci, sz, IransDTables, View, View, vp, ci, vp, View, vp)
     _lib = L
     return L
 
@@ -252,6 +254,7 @@ EXPORTED_SYMBOLS = [
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
     "vc_irans_bound", "vc_irans_wave_words", "vc_irans_encode_host", "vc_irans_decode_host", "vc_irans_pack_tables",
     "vc_irans_tables_in_lds", "vc_irans_encode", "vc_irans_decode_begin", "vc_irans_decode",
+    "vc_irans_decode_eb", "vc_irans_decode_gc",
     # the operator spellings of SURVEY.md 8(b), thin forwards (csrc/abi_aliases.cpp)
     "vc_gdn", "vc_spynet_level", "vc_pool", "vc_upsample", "vc_pad", "vc_blend", "vc_factorized_bits", "vc_gaussian_symbols",
 ]
@@ -1255,10 +1258,9 @@ class IransTables:
         return IransDTables(self.cdf16.data_ptr(), self.rows.data_ptr(), self.n_tables, self.entries)
 
 
-def irans_encode(segments, table_sets, waves=4):
-    """Device encoder (vc_irans_encode): ``segments`` = [(symbols, indexes, table_set)] of int32 CUDA tensors [images, count],
-    ``table_sets`` = [IransTables].  One launch, one read of the images x W word counts, one copy of the used tails; returns one
-    payload (bytes) per image."""
+def irans_encode_launch(segments, table_sets, waves=4):
+    """The launch of :func:`irans_encode` alone: nothing is read back.  Returns the job :func:`irans_encode_collect` takes, so that
+    several payload sets (the two compressors of an LHBDC level) share ONE read of their word counts."""
     if not segments or not irans_waves_ok(waves):
         raise VcError("irans_encode: at least one segment, waves a power of two in 1..16")
     images, dev = int(segments[0][0].shape[0]), segments[0][0].device
@@ -1276,13 +1278,33 @@ def irans_encode(segments, table_sets, waves=4):
     counts = torch.empty(images * waves, dtype=torch.int32, device=dev)
     check(lib().vc_irans_encode(stream(), segs, len(segments), sets, len(table_sets), images, int(waves), out.data_ptr(), cap,
                                 counts.data_ptr()), "vc_irans_encode")
-    used = counts.cpu().numpy().astype(np.int64) & 0xffffffff          # the one synchronisation
+    return out, counts, cap, images, int(waves)
+
+
+def irans_encode_collect(jobs):
+    """One read of the word counts of every job (the one synchronisation), one copy of the used tails; returns, per job, one
+    payload (bytes) per image."""
+    used = torch.cat([j[1] for j in jobs]).cpu().numpy().astype(np.int64) & 0xffffffff
     if (used == 0xffffffff).any():
         raise VcError("vc_irans_encode: a table index is out of range")
-    tails = torch.cat([out[k, cap - int(c):] for k, c in enumerate(used)]).cpu().numpy().tobytes()
-    sizes = IRANS_SUBSTREAM_HEADER + 4 * used.reshape(images, waves)
-    ends = np.concatenate([[0], np.cumsum(sizes.sum(axis=1))])
-    return [tails[ends[j]:ends[j + 1]] for j in range(images)]
+    parts, at = [], 0
+    for out, _, cap, images, waves in jobs:
+        parts.extend(out[k, cap - int(c):] for k, c in enumerate(used[at:at + images * waves]))
+        at += images * waves
+    tails, result, at, pos = torch.cat(parts).cpu().numpy().tobytes(), [], 0, 0
+    for _, _, _, images, waves in jobs:
+        sizes = IRANS_SUBSTREAM_HEADER + 4 * used[at:at + images * waves].reshape(images, waves)
+        ends = pos + np.concatenate([[0], np.cumsum(sizes.sum(axis=1))])
+        result.append([tails[ends[j]:ends[j + 1]] for j in range(images)])
+        at, pos = at + images * waves, int(ends[-1])
+    return result
+
+
+def irans_encode(segments, table_sets, waves=4):
+    """Device encoder (vc_irans_encode): ``segments`` = [(symbols, indexes, table_set)] of int32 CUDA tensors [images, count],
+    ``table_sets`` = [IransTables].  One launch, one read of the images x W word counts, one copy of the used tails; returns one
+    payload (bytes) per image."""
+    return irans_encode_collect([irans_encode_launch(segments, table_sets, waves)])[0]
 
 
 class _PinnedStage:
@@ -1362,6 +1384,41 @@ class IransDecoder:
         else:                                  # (tools/icip_codec_bench.py: the decode kernels alone, from HIP events)
             timer.bracket("irans decode", 0.0, launch, 8.0 * indexes.numel())
         return out
+
+    def _fused(self, key, nbytes, launch):
+        if timer is None:
+            launch()
+        else:                                  # (tools/codec_bench.py: the fused decode kernels alone, from HIP events)
+            timer.bracket(key, 0.0, launch, nbytes)
+
+    def _symbols_out(self, symbols_out, count):
+        if symbols_out is None:
+            return None
+        if symbols_out.dtype != torch.int32 or tuple(symbols_out.shape) != (self.images, count) or not symbols_out.is_contiguous():
+            raise VcError("IransDecoder: symbols_out is a dense int32 tensor [images, count]")
+        return symbols_out.data_ptr()
+
+    def decode_eb(self, tables, eb_params, out_gain, z_hat, symbols_out=None):
+        """The hyper-latent segment, fused (vc_irans_decode_eb): the table of a symbol is its channel's, ``z_hat`` (a T window
+        [images, hz, wz, C]) receives what vc_eb_dequant would write.  ``symbols_out``: int32 [images, C*hz*wz] for tests / traces."""
+        count = z_hat.c * z_hat.h * z_hat.w
+        sym = self._symbols_out(symbols_out, count)
+        self._fused("irans decode eb", 4.0 * self.images * count, lambda: check(lib().vc_irans_decode_eb(
+            stream(), self.buf.data_ptr(), self.states.data_ptr(), self.images, self.waves, count, tables.struct(), eb_params.data_ptr(),
+            None if out_gain is None else out_gain.data_ptr(), z_hat.view(), sym), "vc_irans_decode_eb"))
+        return z_hat
+
+    def decode_gc(self, tables, scales, means, scale_table, out_gain, y_hat, symbols_out=None):
+        """The latent segment, fused (vc_irans_decode_gc): the table index of a symbol comes from ``scales``, ``y_hat`` receives
+        what vc_gc_dequant would write from ``means`` (all three T windows [images, hy, wy, M]).  ``scale_table``: fp32 device
+        tensor of at most 64 entries."""
+        count = y_hat.c * y_hat.h * y_hat.w
+        sym = self._symbols_out(symbols_out, count)
+        self._fused("irans decode gc", 12.0 * self.images * count, lambda: check(lib().vc_irans_decode_gc(
+            stream(), self.buf.data_ptr(), self.states.data_ptr(), self.images, self.waves, count, tables.struct(), scales.view(), means.view(),
+            scale_table.data_ptr(), int(scale_table.numel()), None if out_gain is None else out_gain.data_ptr(), y_hat.view(), sym),
+            "vc_irans_decode_gc"))
+        return y_hat
 
     def finish(self):
         """The one read: VcError when a violation was met or a sub-stream was not consumed to its last word."""

@@ -874,6 +874,36 @@ class MeanScaleHyperprior(_Prepared):
                                           y_hat.view()), "vc_gc_dequant")
         return run_sequential(self.g_s, y_hat, self._cache["g_s"], final_act=final_act)
 
+    # -- the same two halves on the device-coded payload (bitstream.LhbdcStreamCodec(coder="device")) -------
+    def z_index_dev(self, n, shape, device):
+        """the encoder's index tensor of the hyper-latent segment, [n, N*hz*wz] int32 on the device, cached per shape"""
+        key = (int(n), int(shape[0]) * int(shape[1]), str(device))
+        cache = self._cache.setdefault("z_index", {})
+        if key not in cache:
+            cache.clear()
+            idx = torch.arange(self.N, dtype=torch.int32, device=device).view(1, self.N, 1)
+            cache[key] = idx.expand(key[0], self.N, key[1]).reshape(key[0], -1).contiguous()
+        return cache[key]
+
+    def hyper_decode_dev_t(self, dec, shape, gains=(None, None, None, None)):
+        """hyper_decode_t with the hyper-latent segment decoded where it lies: ``dec`` (hip.IransDecoder, one payload per image)
+        writes z_hat itself (vc_irans_decode_eb) -- no symbol tensor, no index tensor.  Returns (scales T, means T): the index of
+        a latent symbol is taken from the scales by the next segment's kernel.  Same _hs_for_bitstream pinning as the host path."""
+        g, ig, hg, hig = gains
+        hz, wz = int(shape[0]), int(shape[1])
+        eb = self.entropy_bottleneck
+        z_hat = T.empty(dec.images, hz, wz, self.N, eb.quantiles.device)
+        dec.decode_eb(eb.irans_tables(), eb.device_params(), hig, z_hat)
+        gp, _ = self._hs_for_bitstream(z_hat)
+        return gp.channels(0, self.M), gp.channels(self.M, 2 * self.M)
+
+    def synth_decode_dev_t(self, dec, scales, means, gains=(None, None, None, None), final_act=None):
+        """synth_decode_t with the latent segment decoded where it lies (vc_irans_decode_gc): scales and means in, y_hat out."""
+        g, ig, hg, hig = gains
+        y_hat = T.empty(means.n, means.h, means.w, self.M, means.buf.device)
+        dec.decode_gc(self.gaussian_conditional.irans_tables(), scales, means, self._scale_table_dev(), ig, y_hat)
+        return run_sequential(self.g_s, y_hat, self._cache["g_s"], final_act=final_act)
+
     def decompress_t(self, strings, shape, device, gains=(None, None, None, None), final_act=None, trace=None):
         """``trace``: a dict that receives the decoder's integers ("z_sym", "y_idx", "y_sym": host int32 [n, count]).
         A ``trace["y_idx_override"]`` entry (int32 [n, count], put there by the caller) replaces the scale-table indexes
