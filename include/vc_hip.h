@@ -270,7 +270,7 @@ int vc_quantize_mask(vc_stream s, vc_view in, vc_view out, const float *gain, in
 /* torchvision.ops.deform_conv2d, modulated (DCNv2), kernel 3x3, stride 1, padding 1, dilation 1, as called at
  * ICIP2024/src/model/helpers.py:56 (DeformConv2d(2C, C, 3, padding=1, groups=16)):
  *   in [n,h,w,G*cg], offset [n,h,w,G*9*2] (per group and tap: dy then dx), mask [n,h,w,G*9] (p==0: all ones),
- *   out [n,h,w,G*og]; conv groups == offset groups == G, cg in {4,8,12,16}, og <= 8.
+ *   out [n,h,w,G*og]; conv groups == offset groups == G; (cg, og) one of (4,2) (4,4) (8,4) (8,8) (12,6) (12,12) (16,4) (16,8).
  * wpk: weights re-laid out by vc_deform_pack_weights ([G][9][cg][og] floats), bias [G*og] or NULL. */
 int vc_deform_pack_weights(const float *w_oihw, int cout, int cin_per_group, int groups, float *dst);
 int vc_deform_conv2d(vc_stream s, vc_view in, vc_view offset, vc_view mask, const float *wpk, const float *bias,
@@ -281,6 +281,16 @@ int vc_deform_conv2d(vc_stream s, vc_view in, vc_view offset, vc_view mask, cons
  * the rest x2.  raw_r [n,h,w,27*G/2], flow_r [n,h,w,2] = (u,v), x_r [n,h,w,(G/2)*cg], out [n,h,w,G*og]. */
 int vc_offset_diversity(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2, vc_view flow2,
                         float magnitude, const float *wpk, const float *bias, int groups, vc_view out);
+/* ICIP2023 DeformB.get_deformed_maps (ICIP2023/src/model/m.py:72-86) in one launch: two plain modulated
+ * DeformConv2d(c, c, 3, padding=1, groups=G/2) layers, one per reference, their outputs concatenated.  For each reference r
+ *   ox, oy, m = chunk(raw_r, 3); offset_r = cat(ox, oy) (used as it comes: no tanh, no magnitude, no flow); mask_r = sigmoid(m)
+ * then deform_conv2d(cat(x1,x2), cat(offset1,offset2), cat(mask1,mask2)) with groups 0..G/2-1 reading x1 and the rest x2.
+ * raw_r [n,h,w,27*G/2], x_r [n,h,w,(G/2)*cg], out [n,h,w,G*og]; wpk: vc_deform_pack_weights of the two layers' weights
+ * concatenated along the output channels, bias likewise (or NULL).  fp32 features only.  VC_EINVAL before any launch: a null
+ * pointer, groups odd or < 2, raw_r.c != 27*G/2, x1.c != x2.c, channel counts that do not divide, a (cg, og) outside the list
+ * above, n/h/w of any input different from out's. */
+int vc_deform_pair(vc_stream s, vc_view x1, vc_view raw1, vc_view x2, vc_view raw2, const float *wpk, const float *bias,
+                   int groups, vc_view out);
 /* fp16 path: the same with HALF-precision features -- x1.p / x2.p point at _Float16 tensors (strides in elements), as
  * vc_to_half writes them.  The deformable fusion (helpers.py:35-58) is bound by its gathers; half features halve them.
  * 8 or 16 channels per group; offsets, modulation, bilinear weights and accumulation stay fp32.  One image of the features

@@ -53,9 +53,18 @@ __device__ __forceinline__ float sigmoid_bf(float x)
 // neighbouring positions: 3.21 -> 2.10 ms on the 128 -> 64 fusion @1088x1920 of the configs[4] frame, bit-identical results.
 // MAXT: 512 when the half has at most 8 groups (the ICIP2024 model: 16 groups) -- leaves the register file for the batched
 // gathers; 1024 (up to 16 groups per half) keeps 128 registers and gathers one tap at a time.
-template <int CG, int OG, bool FUSED, bool VEC, int RV = 1, int MAXT = 1024, bool XH = false>
+// MODE: how a tap's offset / modulation come about -- a compile-time property of the instance, nothing of it is decided in the tap loop.
+//   MODE_GENERIC  offsets and (optional) mask are read as they lie in their tensors (vc_deform_conv2d)
+//   MODE_OD       the raw record of OffsetDiversity: tanh * magnitude + flipped flow, logistic on the mask (vc_offset_diversity*)
+//   MODE_PAIR     the raw record of two plain modulated layers (ICIP2023 DeformB.get_deformed_maps): offsets as they come, logistic
+//                 on the mask, no flow (vc_deform_pair)
+// MODE_OD and MODE_PAIR share the record fetch (FUSED below).
+enum { MODE_GENERIC = 0, MODE_OD = 1, MODE_PAIR = 2 };
+
+template <int CG, int OG, int MODE, bool VEC, int RV = 1, int MAXT = 1024, bool XH = false>
 __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
 {
+    constexpr bool FUSED = MODE != MODE_GENERIC;
     extern __shared__ float wsm_all[];
     const int half = a.groups / 2;
     const bool second = blockIdx.y != 0;
@@ -127,7 +136,7 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
     const float *mp = FUSED ? rec + lane * RS + half * 18 + gl * 9
                             : (M.p ? M.p + view_off(M, n, y, x) + gl * 9 : nullptr);
     float fu = 0.0f, fv = 0.0f;
-    if (FUSED) {
+    if (MODE == MODE_OD) {
         const float *fp = FL.p + view_off(FL, n, y, x);
         fu = fp[0];
         fv = fp[1];
@@ -150,9 +159,11 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
         Tap q;
         float dy = op[2 * k], dx = op[2 * k + 1];
         q.m = 1.0f;
-        if (FUSED) {
+        if (MODE == MODE_OD) {
             dy = tanhf(dy) * a.magnitude + fv;        // flow.flip(1): (v, u) pairs with (dy, dx)
             dx = tanhf(dx) * a.magnitude + fu;
+            q.m = 1.0f / (1.0f + expf(-mp[k]));
+        } else if (MODE == MODE_PAIR) {
             q.m = 1.0f / (1.0f + expf(-mp[k]));
         } else if (mp) {
             q.m = mp[k];
@@ -201,9 +212,11 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
         auto tapv = [&](int k) {
             TapV q;
             float dy = op[2 * k], dx = op[2 * k + 1], m = 1.0f;
-            if (FUSED) {
+            if (MODE == MODE_OD) {
                 dy = fmaf(tanh_bf(dy), a.magnitude, fv);          // flow.flip(1): (v, u) pairs with (dy, dx)
                 dx = fmaf(tanh_bf(dx), a.magnitude, fu);
+                m = sigmoid_bf(mp[k]);
+            } else if (MODE == MODE_PAIR) {
                 m = sigmoid_bf(mp[k]);
             } else if (mp) {
                 m = mp[k];
@@ -379,8 +392,9 @@ inline size_t lds_limit()
     return (size_t)v;
 }
 
-template <int CG, int OG, bool FUSED> int launch(hipStream_t st, const DeformArgs &a_in, bool vec)
+template <int CG, int OG, int MODE> int launch(hipStream_t st, const DeformArgs &a_in, bool vec)
 {
+    constexpr bool FUSED = MODE != MODE_GENERIC;
     DeformArgs a = a_in;
     a.gstride = a.x_half == 2 ? (unsigned)((long long)a.x1.h * a.x1.sh * 2) : (unsigned)(CG * (a.x_half ? 2 : 4));
     const int half = a.groups / 2;
@@ -409,6 +423,23 @@ template <int CG, int OG, bool FUSED> int launch(hipStream_t st, const DeformArg
         return hipGetLastError() == hipSuccess ? VC_OK : VC_ELAUNCH;
     };
     const bool small = half <= 8;
+    if constexpr (CG * OG > 128) {
+        // 12 -> 12 channels per group (ICIP2023 level 3): 144 products per tap and channel next to the gathered values.  The scalar
+        // form does not fit the 128 registers a 1024-thread workgroup leaves a lane (the compiler spilled 384 bytes per lane), so
+        // this pair exists with the 512-thread bound only -- at most 8 groups per reference, which is the model's shape; the vector
+        // form gathers one tap at a time (TB = 1).  fp32 features only.
+        if (!small || a.x_half) return VC_EINVAL;
+        if constexpr (FUSED) {
+            auto ok = [&](const vc_view &v, int w) {
+                return (27 * half) % w == 0 && reinterpret_cast<uintptr_t>(v.p) % (4 * w) == 0 && v.sn % w == 0 && v.sh % w == 0 && v.sw % w == 0;
+            };
+            if (ok(a.off1, 4) && ok(a.off2, 4))
+                return vec ? launch_one(k_deform<CG, OG, MODE, true, 4, 512>) : launch_one(k_deform<CG, OG, MODE, false, 4, 512>);
+            if (ok(a.off1, 2) && ok(a.off2, 2))
+                return vec ? launch_one(k_deform<CG, OG, MODE, true, 2, 512>) : launch_one(k_deform<CG, OG, MODE, false, 2, 512>);
+        }
+        return vec ? launch_one(k_deform<CG, OG, MODE, true, 1, 512>) : launch_one(k_deform<CG, OG, MODE, false, 1, 512>);
+    } else {
     if constexpr (FUSED) {
         // width of the record pieces: what the record length and the alignment of the raw offset tensors allow
         auto ok = [&](const vc_view &v, int w) {
@@ -416,34 +447,37 @@ template <int CG, int OG, bool FUSED> int launch(hipStream_t st, const DeformArg
         };
         const int rv = (ok(a.off1, 4) && ok(a.off2, 4)) ? 4 : ((ok(a.off1, 2) && ok(a.off2, 2)) ? 2 : 1);
         if (a.x_half) {             // half-precision features: the fast fused instance or nothing
-            if constexpr (CG % 4 == 0) {
-                if (vec && small && rv == 4) return launch_one(k_deform<CG, OG, true, true, 4, 512, true>);
+            if constexpr (CG % 4 == 0 && MODE == MODE_OD) {
+                if (vec && small && rv == 4) return launch_one(k_deform<CG, OG, MODE_OD, true, 4, 512, true>);
             }
             return VC_EINVAL;
         }
-        if (vec && small && rv == 4) return launch_one(k_deform<CG, OG, true, true, 4, 512>);
-        if (rv == 4) return vec ? launch_one(k_deform<CG, OG, true, true, 4>) : launch_one(k_deform<CG, OG, true, false, 4>);
-        if (rv == 2) return vec ? launch_one(k_deform<CG, OG, true, true, 2>) : launch_one(k_deform<CG, OG, true, false, 2>);
+        if (vec && small && rv == 4) return launch_one(k_deform<CG, OG, MODE, true, 4, 512>);
+        if (rv == 4) return vec ? launch_one(k_deform<CG, OG, MODE, true, 4>) : launch_one(k_deform<CG, OG, MODE, false, 4>);
+        if (rv == 2) return vec ? launch_one(k_deform<CG, OG, MODE, true, 2>) : launch_one(k_deform<CG, OG, MODE, false, 2>);
     }
-    if (vec && small) return launch_one(k_deform<CG, OG, FUSED, true, 1, 512>);
-    return vec ? launch_one(k_deform<CG, OG, FUSED, true>) : launch_one(k_deform<CG, OG, FUSED, false>);
+    if (vec && small) return launch_one(k_deform<CG, OG, MODE, true, 1, 512>);
+    return vec ? launch_one(k_deform<CG, OG, MODE, true>) : launch_one(k_deform<CG, OG, MODE, false>);
+    }
 }
 
-template <bool FUSED> int dispatch(hipStream_t st, const DeformArgs &a, int cg, int og)
+template <int MODE> int dispatch(hipStream_t st, const DeformArgs &a, int cg, int og)
 {
+    constexpr bool FUSED = MODE != MODE_GENERIC;
     // (half features: pointer and strides -- in halves -- whole 8-byte units.  That is all the gathers need: a group's 2 * cg bytes
     //  start 8-byte aligned anyway (cg = 4, 12: every other group), and a 16-byte gather that is only 8-byte aligned is legal)
     auto aligned8h = [](const vc_view &v) { return (reinterpret_cast<uintptr_t>(v.p) % 8 == 0) && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0; };
     const bool vec = a.x_half ? (cg % 4 == 0 && aligned8h(a.x1) && aligned8h(a.x2)) : (cg % 4 == 0 && aligned16(a.x1) && aligned16(a.x2));
     if (a.x_half && !FUSED) return VC_EINVAL;
     switch (cg * 16 + og) {
-    case 4 * 16 + 2: return launch<4, 2, FUSED>(st, a, vec);
-    case 4 * 16 + 4: return launch<4, 4, FUSED>(st, a, vec);
-    case 8 * 16 + 4: return launch<8, 4, FUSED>(st, a, vec);      // C = 64  (level 1)
-    case 12 * 16 + 6: return launch<12, 6, FUSED>(st, a, vec);    // C = 96  (level 2)
-    case 16 * 16 + 8: return launch<16, 8, FUSED>(st, a, vec);    // C = 128 (level 3)
-    case 8 * 16 + 8: return launch<8, 8, FUSED>(st, a, vec);
-    case 16 * 16 + 4: return launch<16, 4, FUSED>(st, a, vec);
+    case 4 * 16 + 2: return launch<4, 2, MODE>(st, a, vec);
+    case 4 * 16 + 4: return launch<4, 4, MODE>(st, a, vec);
+    case 8 * 16 + 4: return launch<8, 4, MODE>(st, a, vec);      // C = 64  (level 1)
+    case 12 * 16 + 6: return launch<12, 6, MODE>(st, a, vec);    // C = 96  (level 2)
+    case 16 * 16 + 8: return launch<16, 8, MODE>(st, a, vec);    // C = 128 (level 3)
+    case 8 * 16 + 8: return launch<8, 8, MODE>(st, a, vec);
+    case 16 * 16 + 4: return launch<16, 4, MODE>(st, a, vec);
+    case 12 * 16 + 12: return launch<12, 12, MODE>(st, a, vec);   // C = 96  (ICIP2023 level 3: 8 groups per reference)
     }
     return VC_EINVAL;
 }
@@ -485,7 +519,7 @@ extern "C" int vc_deform_conv2d(vc_stream s, vc_view in, vc_view offset, vc_view
     a.wpk = wpk;
     a.bias = bias;
     a.groups = groups;
-    return dispatch<false>(as_stream(s), a, cg, og);
+    return dispatch<MODE_GENERIC>(as_stream(s), a, cg, og);
 }
 
 static int offset_diversity(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2, vc_view flow2, float magnitude,
@@ -547,5 +581,32 @@ static int offset_diversity(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1
     a.magnitude = magnitude;
     a.groups = groups;
     a.x_half = x_half;
-    return dispatch<true>(as_stream(s), a, x1.c / half, out.c / groups);
+    return dispatch<MODE_OD>(as_stream(s), a, x1.c / half, out.c / groups);
+}
+
+// Two plain modulated DeformConv2d(c, c, 3, padding=1, groups=G/2) layers on two inputs with their outputs concatenated (ICIP2023
+// DeformB.get_deformed_maps, m.py:72-86) as ONE grouped deformable convolution with G groups: groups [0, G/2) read x1 with the first
+// layer's weights, groups [G/2, G) read x2 with the second layer's.  raw_r = that reference's half of the offset head, the record
+// [x-block | y-block | mask-block] of 9 * G/2 channels each: cat(x-block, y-block) IS torchvision's offset tensor, the mask block goes
+// through the logistic; no tanh, no magnitude, no flow.  fp32 features only.
+extern "C" int vc_deform_pair(vc_stream s, vc_view x1, vc_view raw1, vc_view x2, vc_view raw2, const float *wpk, const float *bias,
+                              int groups, vc_view out)
+{
+    if (!x1.p || !x2.p || !raw1.p || !raw2.p || !wpk || !out.p) return VC_EINVAL;
+    if (groups < 2 || groups % 2) return VC_EINVAL;
+    const int half = groups / 2;
+    if (x1.c != x2.c || x1.c % half || out.c % groups || raw1.c != 27 * half || raw2.c != 27 * half) return VC_EINVAL;
+    const vc_view *vs[] = {&x1, &x2, &raw1, &raw2};
+    for (const vc_view *v : vs)
+        if (v->h != out.h || v->w != out.w || v->n != out.n) return VC_EINVAL;
+    DeformArgs a = {};
+    a.x1 = x1;
+    a.x2 = x2;
+    a.off1 = raw1;
+    a.off2 = raw2;
+    a.out = out;
+    a.wpk = wpk;
+    a.bias = bias;
+    a.groups = groups;
+    return dispatch<MODE_PAIR>(as_stream(s), a, x1.c / half, out.c / groups);
 }

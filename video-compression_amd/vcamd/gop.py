@@ -306,6 +306,46 @@ def code_sequence_icip2024(model, i_models, load_frame, n_frames, level, h=1080,
     return torch.stack(psnr).tolist(), torch.stack(size).tolist()
 
 
+def code_sequence_icip2023(model, i_models, load_frame, n_frames, level, h=1080, w=1920, intra_size=16, cache_features=True,
+                           msssim=False):
+    """The reference's whole-sequence loop of the ICIP2023 model (ICIP2023/src/test.py:36-94, ``val_sequence_level``):
+    :func:`code_sequence_icip2024` without scales, down-ratio or search -- the same coding order and frame types
+    (get_order_typ_list), I-frames through ``i_models[level]`` (ELIC), B-frames through DeformB on the two decoded frames (clamped
+    to [0,1], at most 32 kept) closest in display order.  ``load_frame(i)`` returns the padded NCHW CUDA frame i.  One frame per
+    pass; the only host sync is the final readback.  Returns (psnr list, size list) indexed by display order, PSNR on
+    uint8-rounded [:h,:w] crops, sizes in bits/(h*w); with ``msssim`` a third list, MS-SSIM of the same crops."""
+    from . import hip, icip2023
+    from .layers import BitCounter
+    order_list, typ_list = icip2023.get_order_typ_list(intra_size, n_frames)
+    psnr, size, mss = [None] * n_frames, [None] * n_frames, [None] * n_frames
+    buffer, buffer_order, feats = [], [], {}
+    for order in order_list:
+        cur = load_frame(order)
+        tc = hip.nchw_to_nhwc(cur)
+        if typ_list[order] == "I":
+            bits = BitCounter(cur.device, max_rows=6)
+            dec = hip.nhwc_to_nchw(i_models[int(level)].forward_device(tc, bits))
+        else:
+            ref1, ref2, o1, o2 = icip2023.select_references(None, order, buffer, buffer_order)
+            t1, t2 = hip.nchw_to_nhwc(ref1), hip.nchw_to_nhwc(ref2)
+            f1 = f2 = None
+            if cache_features:
+                for o, t in ((o1, t1), (o2, t2)):
+                    if o not in feats:
+                        feats[o] = model.feature_extractor.run(t)
+                f1, f2 = [feats[o1]], [feats[o2]]
+            bits = BitCounter(cur.device, max_rows=12)
+            dec = hip.nhwc_to_nchw(model.forward_device(t1, t2, tc, level, bits, feats1=f1, feats2=f2))
+        psnr[order] = psnr_uint8(dec, cur, h, w)
+        size[order] = bits.totals().sum() / float(h * w)
+        if msssim:
+            mss[order] = msssim_uint8(dec, cur, h, w)
+        buffer, buffer_order = icip2023.update_buffer(buffer, buffer_order, hip.clamp01_nchw(dec), order)
+        feats = {o: f for o, f in feats.items() if o in buffer_order}     # frames that left the buffer can go
+    out = (torch.stack(psnr).tolist(), torch.stack(size).tolist())
+    return out + (torch.stack(mss).tolist(),) if msssim else out
+
+
 class GopGraph:
     """One GOP of B-frame coding captured ONCE as a HIP graph and replayed per GOP.
 

@@ -196,6 +196,7 @@ def lib():
     sig("vc_deform_pack_weights", ci, vp, ci, ci, ci, vp)
     sig("vc_deform_conv2d", ci, vp, View, View, View, vp, vp, ci, View)
     sig("vc_offset_diversity", ci, vp, View, View, View, View, View, View, cf, vp, vp, ci, View)
+    sig("vc_deform_pair", ci, vp, View, View, View, View, vp, vp, ci, View)
     sig("vc_offset_diversity_hx", ci, vp, View, View, View, View, View, View, cf, vp, vp, ci, View)
     sig("vc_to_half", ci, vp, View, vp)
     sig("vc_offset_diversity_hxp", ci, vp, View, View, View, View, View, View, cf, vp, vp, ci, View)
@@ -248,7 +249,7 @@ EXPORTED_SYMBOLS = [
     "vc_conv_pack_weights_split", "vc_split3", "vc_split3_pad", "vc_nchw_to_nhwc",
     "vc_nhwc_to_nchw", "vc_u8hwc_to_f32nchw_pad", "vc_f32nchw_to_u8hwc", "vc_avgpool_reflectpad", "vc_maxpool2", "vc_maxpool2_sp3", "vc_avgpool2_sp3", "vc_upsample_bilinear", "vc_upsample_bilinear_sp3", "vc_axpby", "vc_clamp01", "vc_channel_scale", "vc_warp",
     "vc_spynet_preprocess", "vc_spynet_level_input", "vc_spynet_level_input_sp3", "vc_lhbdc_blend", "vc_flex_blend",
-    "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar",
+    "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_deform_pair", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar",
     "vc_attention_gate", "vc_sse_clamp01", "vc_select_flow", "vc_eb_forward", "vc_eb_dequant", "vc_gc_forward", "vc_gc_indexes", "vc_refine_scales",
     "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_gc_forward_ckbd", "vc_gc_indexes_ckbd", "vc_gc_dequant_ckbd", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
@@ -1080,8 +1081,35 @@ class PackedDeform:
         self.bias = None if bias is None else bias.detach().to(device, torch.float32).contiguous()
         self.groups, self.cout, self.cin = groups, cout, cg * groups
 
+    @classmethod
+    def from_pair(cls, layer1, layer2):
+        """Two DeformConv2d(c, c, 3, padding=1, groups=G/2) layers (parameter holders with weight / bias / groups) as ONE packed
+        convolution of G groups for :meth:`pair`: weights and biases concatenated along the output channels."""
+        if layer1.groups != layer2.groups or layer1.weight.shape != layer2.weight.shape or (layer1.bias is None) != (layer2.bias is None):
+            raise VcError("a deformable pair needs two layers of the same shape")
+        bias = None if layer1.bias is None else torch.cat([layer1.bias.detach(), layer2.bias.detach()])
+        return cls(torch.cat([layer1.weight.detach(), layer2.weight.detach()]), bias, 2 * layer1.groups, layer1.weight.device)
+
     def _bias_ptr(self):
         return None if self.bias is None else self.bias.data_ptr()
+
+    def pair(self, x1, raw1, x2, raw2, out=None):
+        """vc_deform_pair: ICIP2023 DeformB.get_deformed_maps in one launch (fp32 features)."""
+        if x1.dtype != "f32" or x2.dtype != "f32":
+            raise VcError("vc_deform_pair reads fp32 features")
+        if out is None:
+            out = T.empty(x1.n, x1.h, x1.w, self.cout, x1.buf.device)
+
+        def launch():
+            check(lib().vc_deform_pair(stream(), x1.view(), raw1.view(), x2.view(), raw2.view(), self.wpk.data_ptr(), self._bias_ptr(),
+                                       self.groups, out.view()), "vc_deform_pair")
+        if timer is None:
+            launch()
+        else:
+            flops = 2.0 * x1.n * x1.h * x1.w * self.cout * (self.cin // self.groups) * 9
+            nbytes = x1.n * x1.h * x1.w * 4.0 * (self.cin + raw1.c + raw2.c + self.cout)
+            timer.bracket(f"deform pair k3 {self.cin}->{self.cout} g{self.groups} @{x1.n}x{x1.h}x{x1.w}", flops, launch, nbytes)
+        return out
 
     def conv(self, x, offset, mask=None, out=None):
         if out is None:

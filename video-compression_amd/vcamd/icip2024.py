@@ -180,11 +180,13 @@ class OffsetDiversity(nn.Module):
 
 
 class MS_Feature(_Seq):
-    def __init__(self):
+    def __init__(self, chans=(64, 96, 128)):
+        """``chans``: widths of the three pyramid levels (ICIP2023's DeformB: 32 / 64 / 96)"""
         super().__init__()
-        self.layer1 = nn.Sequential(conv(3, 64, kernel_size=3, stride=2), *_rbb(64))
-        self.layer2 = nn.Sequential(conv(64, 96, kernel_size=3, stride=2), *_rbb(96))
-        self.layer3 = nn.Sequential(conv(96, 128, kernel_size=3, stride=2), *_rbb(128))
+        c1, c2, c3 = chans
+        self.layer1 = nn.Sequential(conv(3, c1, kernel_size=3, stride=2), *_rbb(c1))
+        self.layer2 = nn.Sequential(conv(c1, c2, kernel_size=3, stride=2), *_rbb(c2))
+        self.layer3 = nn.Sequential(conv(c2, c3, kernel_size=3, stride=2), *_rbb(c3))
 
     def run(self, x, outs=(None, None, None)):
         l1 = self.seq("layer1", x, out=outs[0])
@@ -223,11 +225,12 @@ class FlowNET(_Seq):
 
 
 class _TemporalEnc(_Seq):
-    def __init__(self, mult, N=128, M=128):
+    def __init__(self, mult, N=128, M=128, chans=(64, 96, 128)):
         super().__init__()
-        self.g_a1 = nn.Sequential(conv(64 * mult, N, kernel_size=5, stride=2), *_rbb(N))
-        self.g_a2 = nn.Sequential(conv(N + 96 * mult, N, kernel_size=5, stride=2), *_rbb(N))
-        self.g_a3 = nn.Sequential(conv(N + 128 * mult, M, kernel_size=5, stride=2), *_rbb(M))
+        c1, c2, c3 = chans
+        self.g_a1 = nn.Sequential(conv(c1 * mult, N, kernel_size=5, stride=2), *_rbb(N))
+        self.g_a2 = nn.Sequential(conv(N + c2 * mult, N, kernel_size=5, stride=2), *_rbb(N))
+        self.g_a3 = nn.Sequential(conv(N + c3 * mult, M, kernel_size=5, stride=2), *_rbb(M))
 
     def run(self, l1, l2, l3, out=None):
         y = self.seq("g_a1", l1)
@@ -246,11 +249,15 @@ class ResidualTemproalEnc(_TemporalEnc):
 
 
 class Reconstuctor(_Seq):
-    def __init__(self):
+    def __init__(self, widths=(64, 96, 128), up=None):
+        """``widths``: channels of x_comp_l1 / l2 / l3; ``up(cin, cout)``: the x2 upsampling layer that ends a level (default: the
+        sub-pixel convolution of ICIP2024; ICIP2023 ends its levels with a 3x3 transposed convolution)."""
         super().__init__()
-        self.layer3 = nn.Sequential(*_rbb(128), subpel_conv3x3(128, 128, 2))
-        self.layer2 = nn.Sequential(conv(128 + 96, 96, 1, 1), *_rbb(96), subpel_conv3x3(96, 96, 2))
-        self.layer1 = nn.Sequential(conv(96 + 64, 64, 1, 1), *_rbb(64), subpel_conv3x3(64, 3, 2))
+        w1, w2, w3 = widths
+        up = up or (lambda cin, cout: subpel_conv3x3(cin, cout, 2))
+        self.layer3 = nn.Sequential(*_rbb(w3), up(w3, w3))
+        self.layer2 = nn.Sequential(conv(w3 + w2, w2, 1, 1), *_rbb(w2), up(w2, w2))
+        self.layer1 = nn.Sequential(conv(w2 + w1, w1, 1, 1), *_rbb(w1), up(w1, 3))
 
     def run(self, x_comp_l1, x_comp_l2, x_comp_l3):
         l3 = self.seq("layer3", x_comp_l3)
@@ -293,21 +300,28 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
     """Body shared by Offset_ELIC (enc_mult 5, dec_mult 4, three 432-channel offset heads) and Res_ELIC
     (enc_mult 2, dec_mult 1, residual heads of 64/96/128 channels)."""
 
-    def __init__(self, enc_mult, dec_mult, outs, N=128, M=128):
+    def __init__(self, enc_mult, dec_mult, outs, N=128, M=128, chans=(64, 96, 128), stem=False):
+        """``chans``: widths of the three feature levels the multipliers count in.  ``stem`` (ICIP2023's Res_ELIC): a g_a0 stage
+        takes the frame itself (the first member of ``enc1``) to N channels at half resolution in front of g_a1, which then reads
+        [g_a0 output | rest of enc1]."""
         super().__init__(N, M)
-        self.g_a1 = nn.Sequential(conv(64 * enc_mult, N, kernel_size=5, stride=2), *_rbb(N))
-        self.g_a2 = nn.Sequential(conv(N + 96 * enc_mult, N, kernel_size=5, stride=2), *_rbb(N))
-        self.g_a3 = nn.Sequential(conv(N + 128 * enc_mult, M, kernel_size=5, stride=2), *_rbb(M))
+        c1, c2, c3 = chans
+        self.stem = bool(stem)
+        if stem:
+            self.g_a0 = nn.Sequential(conv(3, N, kernel_size=5, stride=2), *_rbb(N))
+        self.g_a1 = nn.Sequential(conv((N if stem else 0) + c1 * enc_mult, N, kernel_size=5, stride=2), *_rbb(N))
+        self.g_a2 = nn.Sequential(conv(N + c2 * enc_mult, N, kernel_size=5, stride=2), *_rbb(N))
+        self.g_a3 = nn.Sequential(conv(N + c3 * enc_mult, M, kernel_size=5, stride=2), *_rbb(M))
         self.g_s3 = nn.Sequential(*_rbb(M), deconv(M, N, kernel_size=5, stride=2))
-        self.g_o3 = nn.Sequential(conv(N + 128 * dec_mult, N, kernel_size=3, stride=1), *_rbb(N),
+        self.g_o3 = nn.Sequential(conv(N + c3 * dec_mult, N, kernel_size=3, stride=1), *_rbb(N),
                                   conv(N, outs[2], kernel_size=3, stride=1))
-        self.g_s2 = nn.Sequential(conv(N + 128 * dec_mult, N, kernel_size=1, stride=1), *_rbb(N),
+        self.g_s2 = nn.Sequential(conv(N + c3 * dec_mult, N, kernel_size=1, stride=1), *_rbb(N),
                                   deconv(N, N, kernel_size=5, stride=2))
-        self.g_o2 = nn.Sequential(conv(N + 96 * dec_mult, N, kernel_size=3, stride=1), *_rbb(N),
+        self.g_o2 = nn.Sequential(conv(N + c2 * dec_mult, N, kernel_size=3, stride=1), *_rbb(N),
                                   conv(N, outs[1], kernel_size=3, stride=1))
-        self.g_s1 = nn.Sequential(conv(N + 96 * dec_mult, N, kernel_size=1, stride=1), *_rbb(N),
+        self.g_s1 = nn.Sequential(conv(N + c2 * dec_mult, N, kernel_size=1, stride=1), *_rbb(N),
                                   deconv(N, N, kernel_size=5, stride=2))
-        self.g_o1 = nn.Sequential(conv(N + 64 * dec_mult, N, kernel_size=3, stride=1), *_rbb(N),
+        self.g_o1 = nn.Sequential(conv(N + c1 * dec_mult, N, kernel_size=3, stride=1), *_rbb(N),
                                   conv(N, outs[0], kernel_size=3, stride=1))
         self.h_a = nn.Sequential(conv(M, N, stride=1, kernel_size=3), nn.ReLU(inplace=True),
                                  conv(N, N, stride=2, kernel_size=5), nn.ReLU(inplace=True),
@@ -374,7 +388,15 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
             self._caches[key] = pack_conv(self.context_prediction_models[i])
         return self._caches[key]
 
-    def code(self, enc1, enc2, enc3, f1d, f2d, f3d, temporal_into, s, bits, res=(None, None, None), trace=None):
+    def _analysis(self, enc1, enc2, enc3):
+        """g_a1 .. g_a3 (behind g_a0 where the codec has one) on the lists of views whose concatenation the reference feeds them"""
+        if self.stem:
+            enc1 = [self.seq("g_a0", enc1[0])] + list(enc1[1:])
+        y = self.seq_cat("g_a1", enc1) if len(enc1) > 1 else self.seq("g_a1", enc1[0])
+        y = self.seq_cat("g_a2", [y] + list(enc2))
+        return self.seq_cat("g_a3", [y] + list(enc3))
+
+    def code(self, enc1, enc2, enc3, f1d, f2d, f3d, temporal_into, s, bits, res=(None, None, None), trace=None, force=None):
         """Encoder, entropy model and the three decoder heads.
 
         enc1/enc2/enc3: lists of views whose concatenation the reference feeds to g_a1 / (after y) g_a2 / g_a3;
@@ -382,16 +404,19 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         write its output into the given slice of the prior-fusion input; res: optional views added to the three
         heads' outputs (Res_ELIC: x_comp + res fused into the last convolution).  Returns (head1, head2, head3).
         ``trace``: a dict that receives the gained latents "y" / "z" (what the quantiser rounds) and "heads".
+        ``force``: a callable ``force(name, view)`` that sees the gained latents "y" and "z" before anything rounds them and may
+        move them in place -- teacher forcing for stage-wise parity checks on checkpoints whose latents sit next to rounding boundaries.
         Appends 6 x n rows to ``bits`` (n = batch size): z of every image, then y_0 .. y_4 of every image."""
         L = hip.lib()
         M = self.M
         gain, hypergain, invhypergain, invgain = self.interpolate_gain(s)
-        y = self.seq_cat("g_a1", enc1) if len(enc1) > 1 else self.seq("g_a1", enc1[0])
-        y = self.seq_cat("g_a2", [y] + enc2)
-        y = self.seq_cat("g_a3", [y] + enc3)
+        y = self._analysis(enc1, enc2, enc3)
         dev, n, h, w = y.buf.device, y.n, y.h, y.w
         y = hip.channel_scale(y, gain, out=y)
         z = self.seq("h_a", y, final_chscale=hypergain)
+        if force is not None:
+            force("y", y)
+            force("z", z)
         for i in range(n):                                           # one counter row per image and tensor
             hip.check(L.vc_eb_forward(hip.stream(), z.images(i, i + 1).view(), self.entropy_bottleneck.device_params().data_ptr(),
                                       None, None, hip.NULL_VIEW, None, bits.next_row_ptr(), bits.slots, None), "vc_eb_forward")
@@ -521,9 +546,7 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         coded by one launch of vc_irans_encode on the integers where they lie."""
         L, M = hip.lib(), self.M
         gain, hypergain, invhypergain, invgain = self.interpolate_gain(s)
-        y = self.seq_cat("g_a1", enc1) if len(enc1) > 1 else self.seq("g_a1", enc1[0])
-        y = self.seq_cat("g_a2", [y] + enc2)
-        y = self.seq_cat("g_a3", [y] + enc3)
+        y = self._analysis(enc1, enc2, enc3)
         dev, n, h, w = y.buf.device, y.n, y.h, y.w
         y = hip.channel_scale(y, gain, out=y)
         z = self.seq("h_a", y, final_chscale=hypergain)

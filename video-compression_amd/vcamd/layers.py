@@ -233,22 +233,25 @@ def deconv_as_subpel_weights(deconv):
     PixelShuffle(2): output phase (dy,dx) only ever meets taps of matching parity, at most 3x3 of them.
     With w_T[ci, co, ky, kx]:  W3[co*4 + dy*2 + dx, ci, jy, jx] = w_T[ci, co, 4-2*jy+dy, 4-2*jx+dx] (0 if > 4).
     Lets the transposed convolutions of the I-frame codec run on the same MFMA kernel with the
-    pixel-shuffle store fused (36 tap slots for 25 taps)."""
-    if tuple(deconv.kernel_size) != (5, 5) or tuple(deconv.stride) != (2, 2) or tuple(deconv.padding) != (2, 2) \
-            or tuple(deconv.output_padding) != (1, 1):
-        raise hip.VcError("only ConvTranspose2d(k=5, s=2, p=2, output_padding=1) is supported")
-    wt = deconv.weight.detach().to("cpu", torch.float32)          # [cin, cout, 5, 5]
+    pixel-shuffle store fused (36 tap slots for 25 taps).
+    ConvTranspose2d(k=3, stride=2, padding=1, output_padding=1) (the ICIP2023 reconstructor) likewise: output row 2q + dy reads
+    input row q - 1 + jy through tap ky = padding + 2 - 2*jy + dy = 3 - 2*jy + dy where that is one of 0..2 (9 of 36 slots)."""
+    k, p = int(deconv.kernel_size[0]), int(deconv.padding[0])
+    if (k, p) not in ((5, 2), (3, 1)) or tuple(deconv.kernel_size) != (k, k) or tuple(deconv.stride) != (2, 2) \
+            or tuple(deconv.padding) != (p, p) or tuple(deconv.output_padding) != (1, 1):
+        raise hip.VcError("only ConvTranspose2d(k=5, s=2, p=2, output_padding=1) and (k=3, s=2, p=1, output_padding=1) are supported")
+    wt = deconv.weight.detach().to("cpu", torch.float32)          # [cin, cout, k, k]
     cin, cout = wt.shape[0], wt.shape[1]
     w3 = torch.zeros(cout, 2, 2, cin, 3, 3)
     for dy in range(2):
         for dx in range(2):
             for jy in range(3):
-                ky = 4 - 2 * jy + dy
-                if ky > 4:
+                ky = p + 2 - 2 * jy + dy
+                if ky < 0 or ky >= k:
                     continue
                 for jx in range(3):
-                    kx = 4 - 2 * jx + dx
-                    if kx > 4:
+                    kx = p + 2 - 2 * jx + dx
+                    if kx < 0 or kx >= k:
                         continue
                     w3[:, dy, dx, :, jy, jx] = wt[:, :, ky, kx].t()
     bias = None if deconv.bias is None else deconv.bias.detach().to("cpu", torch.float32).repeat_interleave(4)
