@@ -570,6 +570,18 @@ int vc_irans_decode_eb(vc_stream s, const uint32_t *payloads, vc_irans_dstate *s
 int vc_irans_decode_gc(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
                        vc_irans_dtables tables, vc_view scales, vc_view means, const float *scale_table, int n_scales,
                        const float *out_gain, vc_view y_hat, int32_t *symbols_out);
+/* vc_irans_decode_gc on ONE checkerboard parity (the ELIC intra codec's coder="device"; additive to ABI 6): the
+ * fused form of the chain vc_gc_indexes_ckbd -> vc_irans_decode -> vc_gc_dequant_ckbd, bit-identical to it.  Same launch shape,
+ * state struct, round loop, guarantee and LDS use as vc_irans_decode_gc.  Symbol i of an image is element (c, y, xs) of the
+ * squeezed order [c][h][w / 2] that vc_gc_forward_ckbd writes, i = (c * h + y) * (w / 2) + xs, and lives at full-resolution
+ * column x = 2 * xs + ((y ^ parity) & 1); parity 1 = the anchors.  Table index from scales[n, y, x, c] as vc_gc_indexes_ckbd derives
+ * it; y_hat[n, y, x, c] as vc_gc_dequant_ckbd writes it (the de-quantisation of 0 behind a violation); positions of the other
+ * parity are neither read nor written.  symbols_out (nullable): dense [images][count], squeezed order.  The views may be channel
+ * windows of wider tensors; h may be odd.  VC_EINVAL before any launch: null pointers, w odd, parity not 0 or 1,
+ * count != c * h * (w / 2), views of differing shapes, n != images, n_scales outside 2 .. 64. */
+int vc_irans_decode_gc_ckbd(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
+                            vc_irans_dtables tables, vc_view scales, vc_view means, int parity, const float *scale_table, int n_scales,
+                            const float *out_gain, vc_view y_hat, int32_t *symbols_out);
 
 /* ------------------------------------------------------------------------------------------
  * Entry points under the operator names SURVEY.md section 8(b) lists for the boundary.  Thin forwards to the

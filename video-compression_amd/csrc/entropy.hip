@@ -289,7 +289,7 @@ __global__ void __launch_bounds__(ENT_BLOCK) k_gc_forward_ckbd(vc_view yv, vc_vi
     const float kc = -0.70710678118654752440f;  // float(-(2 ** -0.5))
     const int wh = yv.w >> 1;
     ew_for_each<ROWS>(m, yv.n, yv.h, wh, yv.c, [&](int n, int y, int xh, int c) {
-        const int x = 2 * xh + ((y ^ parity) & 1);
+        const int x = ckbd_column(xh, y, parity);
         float v = yv.p[view_off(yv, n, y, x) + c];
         if (in_gain) v *= in_gain[c];
         const float mv = mu.p[view_off(mu, n, y, x) + c];
@@ -337,7 +337,7 @@ __global__ void __launch_bounds__(ENT_BLOCK) k_gc_indexes_ckbd(vc_view sc, int p
 {
     const int wh = sc.w >> 1;
     ew_for_each<ROWS>(m, sc.n, sc.h, wh, sc.c, [&](int n, int y, int xh, int c) {
-        const int x = 2 * xh + ((y ^ parity) & 1);
+        const int x = ckbd_column(xh, y, parity);
         const float s = vc_lower_bound_scale(sc.p[view_off(sc, n, y, x) + c]);
         indexes[(((long long)n * sc.c + c) * sc.h + y) * wh + xh] = scale_index(s, table, n_scales);
     });
@@ -358,7 +358,7 @@ __global__ void __launch_bounds__(ENT_BLOCK) k_gc_dequant_ckbd(const int32_t *__
 {
     const int wh = yh.w >> 1;
     ew_for_each<ROWS>(m, yh.n, yh.h, wh, yh.c, [&](int n, int y, int xh, int c) {
-        const int x = 2 * xh + ((y ^ parity) & 1);
+        const int x = ckbd_column(xh, y, parity);
         yh.p[view_off(yh, n, y, x) + c] =
             vc_gc_dequant_value(symbols[(((long long)n * yh.c + c) * yh.h + y) * wh + xh], mu.p[view_off(mu, n, y, x) + c], out_gain, c);
     });

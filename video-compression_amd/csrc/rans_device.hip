@@ -11,9 +11,10 @@
 // a violation sets the wave's error word (and the image's sticky one, for the host): the wave decodes zeros from there on, every
 // wave of the image from the next launch on -- a wave looks at its siblings' words only as earlier launches left them, so the
 // zeros do not depend on which wave runs first.  The fused forms (vc_irans_decode_eb / vc_irans_decode_gc: the LHBDC stream codec,
-// DESIGN.md section 4e) run the same round loop, take the table index from the channel / the scale and write the de-quantised
-// latent; behind a violation they write the de-quantisation of 0.  vc_irans_tables_in_lds describes all three: the Gaussian form
-// keeps its scale table (64 floats) behind the cdf rows and, for the sets between 64 KiB - 256 bytes and 64 KiB, asks for the
+// DESIGN.md section 4e; vc_irans_decode_gc_ckbd: one checkerboard parity of the ELIC intra codec, section 4g) run the same round
+// loop, take the table index from the channel / the scale and write the de-quantised latent; behind a violation they write the
+// de-quantisation of 0.  vc_irans_tables_in_lds describes all four: the Gaussian forms
+// keep their scale table (64 floats) behind the cdf rows and, for the sets between 64 KiB - 256 bytes and 64 KiB, asks for the
 // 256 bytes past 64 KiB by opting in, so the boundary between the staged and the global form does not move.
 //
 // Encoder: one launch per payload, walking segments, rounds and sub-steps backwards; tables read from global memory and a
@@ -143,14 +144,15 @@ __global__ __launch_bounds__(64) void irans_begin_kernel(const uint32_t *payload
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// Decoder.  ONE round loop (irans_decode_segment) for the three entry points; what differs between them is where a symbol's table
+// Decoder.  ONE round loop (irans_decode_segment) for the four entry points; what differs between them is where a symbol's table
 // index comes from and where the decoded integer goes -- an `Io`:
 //     Item fetch(image, i)                 everything symbol i needs that does NOT depend on the coder state: its table index and
 //                                          whatever the store wants later (a median, a mean, the position)
 //     void store(image, i, item, symbol)   the decoded integer (0 behind a violation) to its destination
 // PlainIo: index tensor in, integer tensor out (vc_irans_decode).  EbIo: the index is the channel i / (h w), the store writes
 // z_hat as vc_eb_dequant would (vc_irans_decode_eb).  GcIo: the index is scale_index of the NHWC scale, the store writes y_hat as
-// vc_gc_dequant would (vc_irans_decode_gc); both through the expressions of entropy_shared.h that entropy.hip itself uses.
+// vc_gc_dequant would (vc_irans_decode_gc); GcCkbdIo: the same struct at one checkerboard parity, symbol i being an element of the
+// squeezed order (vc_irans_decode_gc_ckbd); all through the expressions of entropy_shared.h that entropy.hip itself uses.
 // fetch() for round r + 1 is issued before the state chain of round r (state -> cumulative value -> search -> state -> words), so
 // its loads (and the 63 compares of scale_index) are in flight while that chain is waited on.
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -199,19 +201,25 @@ struct EbIo {
     }
 };
 
-struct GcIo {
+// kCkbd = false: symbol i = element (c, y, x) of the NCHW raster of the views.  kCkbd = true: one checkerboard parity of them -- symbol
+// i = element (c, y, xs) of the squeezed order [c][h][w/2] that vc_gc_forward_ckbd writes (`ras` describes that order), at
+// full-resolution column ckbd_column(xs, y, parity); the other parity is neither read nor written.
+template <bool kCkbd>
+struct GcIoT {
     struct Item { int32_t index; float mean; int c, y, x; };
     Raster ras;
     vc_view sc, mu, yh;
     const float *table;                        // the scale table, staged in LDS by the kernel
     int n_scales;
     const float *out_gain;
-    int32_t *symbols;                          // nullable: dense [images][count]
+    int32_t *symbols;                          // nullable: dense [images][count], in symbol order
     uint32_t count;
+    int parity;                                // kCkbd only
     __device__ __forceinline__ Item fetch(int image, uint32_t i) const
     {
         Item it;
         ras.split(i, it.c, it.y, it.x);
+        if (kCkbd) it.x = ckbd_column(it.x, it.y, parity);
         it.index = scale_index(vc_lower_bound_scale(sc.p[view_off(sc, image, it.y, it.x) + it.c]), table, n_scales);
         it.mean = mu.p[view_off(mu, image, it.y, it.x) + it.c];
         return it;
@@ -222,6 +230,8 @@ struct GcIo {
         if (symbols) symbols[static_cast<size_t>(image) * count + i] = symbol;
     }
 };
+using GcIo = GcIoT<false>;
+using GcCkbdIo = GcIoT<true>;
 
 // One segment of one (image, wave): `staged` = the workgroup's LDS for the cdf rows (kLds) -- whatever else a kernel keeps in LDS it
 // has written AND synchronised before it calls this.
@@ -345,10 +355,10 @@ __global__ __launch_bounds__(64) void irans_decode_eb_kernel(const uint32_t *pay
     irans_decode_segment<kLds>(payloads, states, waves, count, tab, irans_lds, io);
 }
 
-// LDS: the cdf rows (kLds; 2 * entries bytes, a multiple of 16), then the kScaleSlots floats of the scale table
-template <bool kLds>
+// LDS: the cdf rows (kLds; 2 * entries bytes, a multiple of 16), then the kScaleSlots floats of the scale table.  Io: GcIo / GcCkbdIo
+template <bool kLds, class Io>
 __global__ __launch_bounds__(64) void irans_decode_gc_kernel(const uint32_t *payloads, vc_irans_dstate *states, int waves, uint32_t count,
-                                                             const vc_irans_dtables tab, GcIo io)
+                                                             const vc_irans_dtables tab, Io io)
 {
     float *table = reinterpret_cast<float *>(irans_lds + (kLds ? tab.entries : 0));
     if (static_cast<int>(threadIdx.x) < io.n_scales) table[threadIdx.x] = io.table[threadIdx.x];      // n_scales <= kScaleSlots = 64 lanes
@@ -457,6 +467,29 @@ extern "C" int vc_irans_decode_eb(vc_stream s, const uint32_t *payloads, vc_iran
     return VC_OK;
 }
 
+namespace {
+// the launch of the two Gaussian forms: same grid, same LDS layout (one opt-in per instantiation)
+template <class Io>
+int launch_decode_gc(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
+                     const vc_irans_dtables &tables, const Io &io)
+{
+    const dim3 grid(images * waves), block(irl::kLanes);
+    constexpr size_t table_bytes = kScaleSlots * sizeof(float);
+    if (vc_irans_tables_in_lds(tables.entries)) {
+        static vc_lds_raised raised;           // (only the sets within 256 bytes of 64 KiB get here past the default limit)
+        const size_t lds = 2 * static_cast<size_t>(tables.entries) + table_bytes;
+        if (!vc_raise_lds_limit(reinterpret_cast<const void *>(&irans_decode_gc_kernel<true, Io>), lds, raised)) return VC_ELAUNCH;
+        hipLaunchKernelGGL((irans_decode_gc_kernel<true, Io>), grid, block, lds, as_stream(s), payloads, states, waves,
+                           static_cast<uint32_t>(count), tables, io);
+    } else {
+        hipLaunchKernelGGL((irans_decode_gc_kernel<false, Io>), grid, block, table_bytes, as_stream(s), payloads, states, waves,
+                           static_cast<uint32_t>(count), tables, io);
+    }
+    VC_LAUNCH_CHECK();
+    return VC_OK;
+}
+}  // namespace
+
 extern "C" int vc_irans_decode_gc(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
                                   vc_irans_dtables tables, vc_view scales, vc_view means, const float *scale_table, int n_scales,
                                   const float *out_gain, vc_view y_hat, int32_t *symbols_out)
@@ -466,19 +499,22 @@ extern "C" int vc_irans_decode_gc(vc_stream s, const uint32_t *payloads, vc_iran
         !same_shape(means, y_hat) || !fused_count_ok(y_hat, count))
         return VC_EINVAL;
     const GcIo io = {{static_cast<uint32_t>(y_hat.h) * static_cast<uint32_t>(y_hat.w), static_cast<uint32_t>(y_hat.w)}, scales, means, y_hat,
-                     scale_table, n_scales, out_gain, symbols_out, static_cast<uint32_t>(count)};
-    const dim3 grid(images * waves), block(irl::kLanes);
-    constexpr size_t table_bytes = kScaleSlots * sizeof(float);
-    if (vc_irans_tables_in_lds(tables.entries)) {
-        static vc_lds_raised raised;           // (only the sets within 256 bytes of 64 KiB get here past the default limit)
-        const size_t lds = 2 * static_cast<size_t>(tables.entries) + table_bytes;
-        if (!vc_raise_lds_limit(reinterpret_cast<const void *>(&irans_decode_gc_kernel<true>), lds, raised)) return VC_ELAUNCH;
-        hipLaunchKernelGGL(irans_decode_gc_kernel<true>, grid, block, lds, as_stream(s), payloads, states, waves, static_cast<uint32_t>(count),
-                           tables, io);
-    } else {
-        hipLaunchKernelGGL(irans_decode_gc_kernel<false>, grid, block, table_bytes, as_stream(s), payloads, states, waves,
-                           static_cast<uint32_t>(count), tables, io);
-    }
-    VC_LAUNCH_CHECK();
-    return VC_OK;
+                     scale_table, n_scales, out_gain, symbols_out, static_cast<uint32_t>(count), 0};
+    return launch_decode_gc(s, payloads, states, images, waves, count, tables, io);
+}
+
+extern "C" int vc_irans_decode_gc_ckbd(vc_stream s, const uint32_t *payloads, vc_irans_dstate *states, int images, int waves, size_t count,
+                                       vc_irans_dtables tables, vc_view scales, vc_view means, int parity, const float *scale_table,
+                                       int n_scales, const float *out_gain, vc_view y_hat, int32_t *symbols_out)
+{
+    if (!fused_common_ok(payloads, states, images, waves, tables) || !scale_table || n_scales < 2 || n_scales > kScaleSlots ||
+        !fused_view_ok(y_hat, images) || !fused_view_ok(scales, images) || !fused_view_ok(means, images) || !same_shape(scales, y_hat) ||
+        !same_shape(means, y_hat) || (parity != 0 && parity != 1) || (y_hat.w & 1))
+        return VC_EINVAL;
+    vc_view half = y_hat;                      // the squeezed order's shape: count == c * h * (w / 2)
+    half.w = y_hat.w / 2;
+    if (!fused_count_ok(half, count)) return VC_EINVAL;
+    const GcCkbdIo io = {{static_cast<uint32_t>(half.h) * static_cast<uint32_t>(half.w), static_cast<uint32_t>(half.w)}, scales, means, y_hat,
+                         scale_table, n_scales, out_gain, symbols_out, static_cast<uint32_t>(count), parity};
+    return launch_decode_gc(s, payloads, states, images, waves, count, tables, io);
 }

@@ -547,3 +547,139 @@ def unpack_icip2024_frame_dev(data):
         raise hip.VcError(f"ICIP2024 device-coded container: payload lengths {n_off} + {n_res} do not fit {len(data)} bytes / {waves} waves")
     strings = {"offset": [data[fixed:fixed + n_off]], "residual": [data[fixed + n_off:]]}
     return {"strings": strings, "waves": waves, "shape": (hz, wz), "down_ratio": down_ratio, "s": s, "scale1": scale1, "scale2": scale2}
+
+
+# ------------------------------------------------------------------------------------------------
+# ICIP2024 sequence file: device-coded ELIC I-frames (VCII) and B-frames (VCID) in coding order (VCSQ).  Layout: INTEGRATION.md
+# ------------------------------------------------------------------------------------------------
+# I-frame container, little-endian:
+#   offset  0  4 bytes  magic "VCII"
+#           4  u8       version (1)
+#           5  u8       waves W (1, 2, 4, 8 or 16)
+#           6  u16 x 2  hyper-latent shape (h, w) = frame / 64
+#          10  u32      payload length
+#          14  the payload of ELIC.compress(coder="device") for one image
+ICIP2024_INTRA_MAGIC = b"VCII"
+ICIP2024_INTRA_VERSION = 1
+ICIP2024_INTRA_HEADER = struct.Struct("<4sBBHHI")
+
+
+def pack_icip2024_intra_dev(payload, shape, waves):
+    """The container of one image of an ``ELIC.compress(coder="device")`` result: its payload, "shape" and "waves"."""
+    hz, wz = int(shape[0]), int(shape[1])
+    payload = bytes(payload)
+    if not (1 <= hz <= 0xffff and 1 <= wz <= 0xffff) or not hip.irans_waves_ok(waves):
+        raise hip.VcError(f"hyper-latent shape {hz}x{wz} / waves {waves} do not fit the container")
+    if len(payload) > 0xffffffff or len(payload) % 4 or len(payload) < int(waves) * hip.IRANS_SUBSTREAM_HEADER:
+        raise hip.VcError(f"a payload of {len(payload)} bytes is not one of the interleaved coder with {waves} waves")
+    return ICIP2024_INTRA_HEADER.pack(ICIP2024_INTRA_MAGIC, ICIP2024_INTRA_VERSION, int(waves), hz, wz, len(payload)) + payload
+
+
+def unpack_icip2024_intra_dev(data):
+    """Inverse of :func:`pack_icip2024_intra_dev`: ``{"payload", "waves", "shape"}``; magic, version, the wave count, the smallest
+    possible payload and the total length are validated before anything is returned (VcError)."""
+    data = bytes(data)
+    fixed = ICIP2024_INTRA_HEADER.size
+    if len(data) < fixed:
+        raise hip.VcError(f"ICIP2024 I-frame container: {len(data)} bytes is shorter than the {fixed}-byte header")
+    magic, version, waves, hz, wz, length = ICIP2024_INTRA_HEADER.unpack_from(data, 0)
+    if magic != ICIP2024_INTRA_MAGIC:
+        raise hip.VcError(f"ICIP2024 I-frame container: magic {magic!r} is not {ICIP2024_INTRA_MAGIC!r}")
+    if version != ICIP2024_INTRA_VERSION:
+        raise hip.VcError(f"ICIP2024 I-frame container: version {version} (this reader knows {ICIP2024_INTRA_VERSION})")
+    if not hip.irans_waves_ok(waves):
+        raise hip.VcError(f"ICIP2024 I-frame container: waves {waves} is not a power of two in 1..16")
+    if hz < 1 or wz < 1:
+        raise hip.VcError(f"ICIP2024 I-frame container: hyper-latent shape {hz}x{wz} out of range")
+    if fixed + length != len(data) or length % 4 or length < waves * hip.IRANS_SUBSTREAM_HEADER:
+        raise hip.VcError(f"ICIP2024 I-frame container: payload length {length} does not fit {len(data)} bytes / {waves} waves")
+    return {"payload": data[fixed:], "waves": waves, "shape": (hz, wz)}
+
+
+# Sequence file, little-endian:
+#   offset  0  4 bytes  magic "VCSQ"
+#           4  u8       version (1)
+#           5  u8       model family (1 = ICIP2024; every other value is refused)
+#           6  u16 x 2  picture width, height (unpadded)
+#          10  u32      frame count
+#          14  u16      intra_size
+#          16  f32      quality level s
+#          20  u8       intra quality index
+#          21  one record per frame in CODING order:  u8 type (0 = I, 1 = B) | u32 display order | u32 length | VCII / VCID bytes
+SEQUENCE_MAGIC = b"VCSQ"
+SEQUENCE_VERSION = 1
+SEQUENCE_FAMILY_ICIP2024 = 1
+SEQUENCE_HEADER = struct.Struct("<4sBBHHIHfB")
+SEQUENCE_RECORD = struct.Struct("<BII")
+SEQUENCE_TYPES = ("I", "B")
+
+
+def sequence_plan(intra_size, n_frames):
+    """[(display order, "I" | "B")] in coding order, as the encoder's loop walks it (icip2024.get_order_typ_list).  VcError where
+    that function gives no coding order for the pair: every frame exactly once, the first one an I-frame."""
+    from . import icip2024
+    intra_size, n_frames = int(intra_size), int(n_frames)
+    if intra_size < 1 or n_frames < 1:
+        raise hip.VcError(f"intra_size {intra_size} / {n_frames} frames: both at least 1")
+    if n_frames == 1:
+        return [(0, "I")]
+    order, typ = icip2024.get_order_typ_list(intra_size, n_frames)
+    if sorted(order) != list(range(n_frames)) or len(typ) != n_frames or typ[order[0]] != "I":
+        raise hip.VcError(f"get_order_typ_list({intra_size}, {n_frames}) is no coding order of {n_frames} frames: {order}")
+    return [(o, typ[o]) for o in order]
+
+
+def pack_sequence(records, width, height, intra_size, s, intra_quality, family=SEQUENCE_FAMILY_ICIP2024):
+    """``records``: [(type "I" | "B", display order, container bytes)] in coding order -- checked against :func:`sequence_plan`."""
+    records = [(t, int(o), bytes(b)) for t, o, b in records]
+    if family != SEQUENCE_FAMILY_ICIP2024:
+        raise hip.VcError(f"sequence file: model family {family} (only {SEQUENCE_FAMILY_ICIP2024} = ICIP2024 is defined)")
+    if not (1 <= int(width) <= 0xffff and 1 <= int(height) <= 0xffff and 1 <= int(intra_size) <= 0xffff and 0 <= int(intra_quality) <= 0xff) \
+            or not np.isfinite(float(s)) or not 1 <= len(records) <= 0xffffffff:
+        raise hip.VcError("sequence file: a header field is out of range")
+    if [(o, t) for t, o, _ in records] != sequence_plan(intra_size, len(records)):
+        raise hip.VcError("sequence file: the records are not in the coding order of get_order_typ_list")
+    if any(len(b) > 0xffffffff for _, _, b in records):
+        raise hip.VcError("sequence file: a frame is longer than the 32-bit length field")
+    head = SEQUENCE_HEADER.pack(SEQUENCE_MAGIC, SEQUENCE_VERSION, family, int(width), int(height), len(records), int(intra_size), float(s),
+                                int(intra_quality))
+    return head + b"".join(SEQUENCE_RECORD.pack(SEQUENCE_TYPES.index(t), o, len(b)) + b for t, o, b in records)
+
+
+def unpack_sequence(data):
+    """Inverse of :func:`pack_sequence`: ``{"family", "width", "height", "frames", "intra_size", "s", "intra_quality", "records":
+    [(type, display order, container bytes)] in coding order}``.  Magic, version, family, field ranges, the frame count against the
+    buffer's length (before anything is sized by it), every record's length against the data that is left, the record sequence
+    against :func:`sequence_plan` and the absence of trailing bytes are validated before anything is returned (VcError)."""
+    data = bytes(data)
+    fixed = SEQUENCE_HEADER.size
+    if len(data) < fixed:
+        raise hip.VcError(f"sequence file: {len(data)} bytes is shorter than the {fixed}-byte header")
+    magic, version, family, width, height, frames, intra_size, s, intra_quality = SEQUENCE_HEADER.unpack_from(data, 0)
+    if magic != SEQUENCE_MAGIC:
+        raise hip.VcError(f"sequence file: magic {magic!r} is not {SEQUENCE_MAGIC!r}")
+    if version != SEQUENCE_VERSION:
+        raise hip.VcError(f"sequence file: version {version} (this reader knows {SEQUENCE_VERSION})")
+    if family != SEQUENCE_FAMILY_ICIP2024:
+        raise hip.VcError(f"sequence file: model family {family} (only {SEQUENCE_FAMILY_ICIP2024} = ICIP2024 is defined)")
+    if width < 1 or height < 1 or intra_size < 1 or not np.isfinite(s):
+        raise hip.VcError(f"sequence file: picture {width}x{height} / intra_size {intra_size} / level {s} out of range")
+    if frames < 1 or fixed + frames * SEQUENCE_RECORD.size > len(data):
+        raise hip.VcError(f"sequence file: {frames} frames do not fit {len(data)} bytes")
+    plan = sequence_plan(intra_size, frames)
+    records, pos = [], fixed
+    for k, (order, typ) in enumerate(plan):
+        if pos + SEQUENCE_RECORD.size > len(data):
+            raise hip.VcError(f"sequence file: the data ends before record {k} of {frames}")
+        t, o, length = SEQUENCE_RECORD.unpack_from(data, pos)
+        pos += SEQUENCE_RECORD.size
+        if t >= len(SEQUENCE_TYPES) or (o, SEQUENCE_TYPES[t]) != (order, typ):
+            raise hip.VcError(f"sequence file: record {k} is (order {o}, type {t}), the coding order asks for ({order}, {typ})")
+        if length > len(data) - pos:
+            raise hip.VcError(f"sequence file: record {k} asks for {length} bytes, {len(data) - pos} are left")
+        records.append((typ, o, data[pos:pos + length]))
+        pos += length
+    if pos != len(data):
+        raise hip.VcError(f"sequence file: {len(data) - pos} trailing bytes behind the last record")
+    return {"family": family, "width": width, "height": height, "frames": frames, "intra_size": intra_size, "s": s,
+            "intra_quality": intra_quality, "records": records}

@@ -3,11 +3,17 @@
     python -m vcamd.cli encode_B --ref_1 frames/ref_1.png --ref_2 frames/ref_2.png --current frames/current.png --bin bits_B.bin --l 1626
     python -m vcamd.cli decode_B --ref_1 frames/ref_1.png --ref_2 frames/ref_2.png --bin bits_B.bin [--out decoded.png]
     python -m vcamd.cli test --test_path /datasets/UVG/full_test/ --b_pretrained ../new_compression_1626.pth --lmbda 1626
+    python -m vcamd.cli encode_seq --frames DIR --out FILE --level S [--intra_size 16] [--weights B.pth --i_weights I.pth | --seeded N]
+    python -m vcamd.cli decode_seq --bin FILE --out DIR [--weights B.pth --i_weights I.pth | --seeded N]
 
 ``encode_B`` / ``decode_B`` mirror LHBDC/encode_B.py:21-28,108-126 and LHBDC/decode_B.py:23-28,88-124 (same argument
 names and defaults, same ``bits_B.bin`` container, ``decoded.png`` written beside the bitstream); ``test`` mirrors the
 argument parser and the loop of LHBDC/test/testing.py:35-59,89-196 on top of ``vcamd.data.SequenceReader``; ``test --msssim`` adds
 an MS-SSIM column (pytorch-msssim ``ms_ssim`` defaults on the same uint8 crops, computed on the device) to every line it prints.
+
+``encode_seq`` / ``decode_seq`` are the ICIP2024 models as a whole-sequence codec (vcamd.sequence): the PNGs of a folder, in name
+order, into one ``VCSQ`` file (device-coded ELIC I-frames and FlowGuidedB B-frames) and back into ``im00001.png`` ... of the unpadded
+picture, from the file and the two checkpoints alone.
 
 Checkpoints: ``--weights`` (default ``pretrained_weights/compression_<l>.pth``, as the reference) is loaded with
 ``torch.load(...)["state_dict"]``.  The reference's checkpoints live on Google Drive; where none is present ``--seeded
@@ -134,6 +140,50 @@ def cmd_test(args):
     return summary
 
 
+def _seq_codec(args, dev):
+    from vcamd import sequence
+    model, intra = sequence.load_models(args.seeded, args.weights, args.i_weights, dev)
+    return sequence.Icip2024SequenceCodec(model, intra, waves=args.waves, intra_quality=args.i_qual)
+
+
+def cmd_encode_seq(args):
+    dev = _device()
+    names = sorted(n for n in os.listdir(args.frames) if n.lower().endswith(".png"))
+    if not names:
+        raise hip.VcError(f"{args.frames}: no PNG frames")
+    first = read_png(os.path.join(args.frames, names[0]))
+    h, w = first.shape[:2]
+
+    def load_frame(i):
+        rgb = first if i == 0 else read_png(os.path.join(args.frames, names[i]))
+        if rgb.shape[:2] != (h, w):
+            raise hip.VcError(f"{names[i]}: {rgb.shape[1]}x{rgb.shape[0]}, the sequence is {w}x{h}")
+        return hip.frame_from_uint8(torch.from_numpy(rgb).to(dev))
+    codec = _seq_codec(args, dev)
+    with torch.no_grad():
+        data, _ = codec.encode(load_frame, len(names), args.level, h, w, intra_size=args.intra_size)
+    with open(args.out, "wb") as f:
+        f.write(data)
+    print(f"{args.out}: {len(names)} frames, {len(data)} bytes ({8.0 * len(data) / (len(names) * h * w):.4f} bpp)")
+    return data
+
+
+def cmd_decode_seq(args):
+    from vcamd import bitstream, sequence
+    dev = _device()
+    with open(args.bin, "rb") as f:
+        data = f.read()
+    head = bitstream.unpack_sequence(data)
+    codec = _seq_codec(args, dev)
+    with torch.no_grad():
+        frames = codec.decode(data)
+    os.makedirs(args.out, exist_ok=True)
+    for order in sorted(frames):
+        write_png(os.path.join(args.out, f"im{order + 1:05d}.png"), sequence.crop_uint8(frames[order], head["height"], head["width"]))
+    print(f"{args.out}: {len(frames)} frames of {head['width']}x{head['height']} from {len(data)} bytes")
+    return frames
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m vcamd.cli", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -177,6 +227,27 @@ def build_parser():
     t.add_argument("--seeded", type=int, default=None)
     t.add_argument("--msssim", action="store_true", help="also report MS-SSIM (pytorch-msssim ms_ssim defaults, data range 255) per sequence, level and overall")
     t.set_defaults(fn=cmd_test)
+
+    def seq_ckpt(p):
+        p.add_argument("--weights", default=None, help="FlowGuidedB checkpoint (a state dict, or one under 'state_dict')")
+        p.add_argument("--i_weights", default=None, help="ELIC checkpoint of the I-frames")
+        p.add_argument("--seeded", type=int, default=None, help="use the synthetic checkpoints of vcamd.seeding with this seed instead")
+        p.add_argument("--i_qual", type=int, default=0, help="quality index of the I-frame checkpoint, carried in the file and checked by decode_seq")
+        p.add_argument("--waves", type=int, default=4, help="sub-streams per payload of the device coder")
+
+    es = sub.add_parser("encode_seq", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    es.add_argument("--frames", required=True, help="folder of PNG frames, coded in name order")
+    es.add_argument("--out", required=True, help="the VCSQ file to write")
+    es.add_argument("--level", type=float, required=True, help="quality level s of the B-frames")
+    es.add_argument("--intra_size", type=int, default=16)
+    seq_ckpt(es)
+    es.set_defaults(fn=cmd_encode_seq)
+
+    ds = sub.add_parser("decode_seq", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ds.add_argument("--bin", required=True, help="the VCSQ file")
+    ds.add_argument("--out", required=True, help="folder for im00001.png ...")
+    seq_ckpt(ds)
+    ds.set_defaults(fn=cmd_decode_seq)
     return ap
 
 

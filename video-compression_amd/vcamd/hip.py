@@ -238,6 +238,7 @@ def lib():
     sig("vc_irans_decode", ci, vp, vp, vp, ci, ci, vp, sz, IransDTables, vp)
     sig("vc_irans_decode_eb", ci, vp, vp, vp, ci, ci, sz, IransDTables, vp, vp, View, vp)
     sig("vc_irans_decode_gc", ci, vp, vp, vp, ci, ci, sz, IransDTables, View, View, vp, ci, vp, View, vp)
+    sig("vc_irans_decode_gc_ckbd", ci, vp, vp, vp, ci, ci, sz, IransDTables, View, View, ci, vp, ci, vp, View, vp)
     _lib = L
     return L
 
@@ -255,7 +256,7 @@ EXPORTED_SYMBOLS = [
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
     "vc_irans_bound", "vc_irans_wave_words", "vc_irans_encode_host", "vc_irans_decode_host", "vc_irans_pack_tables",
     "vc_irans_tables_in_lds", "vc_irans_encode", "vc_irans_decode_begin", "vc_irans_decode",
-    "vc_irans_decode_eb", "vc_irans_decode_gc",
+    "vc_irans_decode_eb", "vc_irans_decode_gc", "vc_irans_decode_gc_ckbd",
     # the operator spellings of SURVEY.md 8(b), thin forwards (csrc/abi_aliases.cpp)
     "vc_gdn", "vc_spynet_level", "vc_pool", "vc_upsample", "vc_pad", "vc_blend", "vc_factorized_bits", "vc_gaussian_symbols",
 ]
@@ -1446,6 +1447,19 @@ class IransDecoder:
             stream(), self.buf.data_ptr(), self.states.data_ptr(), self.images, self.waves, count, tables.struct(), scales.view(), means.view(),
             scale_table.data_ptr(), int(scale_table.numel()), None if out_gain is None else out_gain.data_ptr(), y_hat.view(), sym),
             "vc_irans_decode_gc"))
+        return y_hat
+
+    def decode_gc_ckbd(self, tables, scales, means, parity, scale_table, out_gain, y_hat, symbols_out=None):
+        """One checkerboard parity of the latent segment, fused (vc_irans_decode_gc_ckbd): the symbols are in the squeezed order
+        vc_gc_forward_ckbd writes, the table index of each comes from ``scales`` at its full-resolution position, ``y_hat`` receives
+        what vc_gc_dequant_ckbd would write from ``means`` there and keeps the other parity (all three T windows [images, hy, wy, C],
+        wy even).  ``symbols_out``: int32 [images, C*hy*wy/2] for tests / traces."""
+        count = y_hat.c * y_hat.h * (y_hat.w // 2)
+        sym = self._symbols_out(symbols_out, count)
+        self._fused("irans decode gc ckbd", 12.0 * self.images * count, lambda: check(lib().vc_irans_decode_gc_ckbd(
+            stream(), self.buf.data_ptr(), self.states.data_ptr(), self.images, self.waves, count, tables.struct(), scales.view(), means.view(),
+            int(parity), scale_table.data_ptr(), int(scale_table.numel()), None if out_gain is None else out_gain.data_ptr(), y_hat.view(), sym),
+            "vc_irans_decode_gc_ckbd"))
         return y_hat
 
     def finish(self):

@@ -644,7 +644,8 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
     def _decompress_t_uploaded(self, dec, hz, wz, f1d, f2d, f3d, temporal_into, invhypergain, invgain, res, trace):
         """decompress_t on the payloads of ``coder="device"``, already uploaded (hip.IransDecoder): every pass is vc_gc_indexes_ckbd ->
         vc_irans_decode -> vc_gc_dequant_ckbd on the device, nothing crosses to the host (the caller reads the decoder's error
-        words once, after the reconstruction)."""
+        words once, after the reconstruction).  The fused vc_irans_decode_gc_ckbd measured slower than this chain here (DESIGN.md section
+        4g), so the B-frame decoders stay on the chain."""
         L, M = hip.lib(), self.M
         dev = self.Gain.device
         if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
@@ -860,9 +861,129 @@ class ELIC(JointAutoregressiveHierarchicalPriors):
             gc._packed = gc.scale_table.detach().float().contiguous().to(gc.scale_bound.device)
         return gc._packed
 
-    def compress(self, x):
-        """{"strings": [[[g0], [g1], [g2], [g3], [g4]], [z]], "shape", "y_hat": 5 NCHW tensors} like elic.py:307-414."""
+    # ---- the same codec with the interleaved coder on the device (coder="device") -------------------------
+    # One payload per image: the hyper-latent segment (table set 0, index = channel), then the ten passes (table set 1) in coding
+    # order -- group 0 anchors, group 0 non-anchors, ... -- the segment table of _Elic.compress_t.  The two passes of a group fill
+    # ONE zero-initialised y_hat where it lies (vc_gc_forward_ckbd / vc_irans_decode_gc_ckbd): no parity mask, no merge, no numpy
+    # and nothing crosses to the host before the payloads are collected / the error words are read.
+    CODERS = ("host", "device")
+
+    def _check_coder(self, coder, waves):
+        if coder not in self.CODERS or not hip.irans_waves_ok(waves):
+            raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {self.CODERS}, waves a power of two in 1..16")
+
+    def _device_passes(self, hyper, y_hat):
+        """The ten entropy-parameter passes in coding order: yields (group, c0, c1, parity, scales, means).  The caller fills
+        ``y_hat`` (zero-initialised) at the pass's parity of channels c0:c1 before it asks for the next pass.  Encoder and decoder
+        both walk this one generator: the same launches on the same layouts."""
+        M = self.M
+        n, h, w, dev = hyper.n, hyper.h, hyper.w, hyper.buf.device
+        pin = T.empty(n, h, w, 6 * M, dev)                             # [ctx | channel ctx | hyper]
+        hip.axpby(hyper, None, out=pin.channels(4 * M, 6 * M))
+        pin0 = T.empty(n, h, w, 4 * M, dev)                            # group 0: [ctx | hyper]
+        hip.axpby(hyper, None, out=pin0.channels(2 * M, 4 * M))
+        bounds = ELIC_GROUPS + (M,)
+        for i in range(5):
+            c0, c1 = bounds[i], bounds[i + 1]
+            cg = c1 - c0
+            p = pin0 if i == 0 else pin
+            hip.axpby(hyper, None, alpha=0.0, out=p.channels(0, 2 * M))   # anchor pass: ctx = 0 (hyper is finite), as _param_buffers
+            if i > 0:
+                self._sub("channel_context_models", i - 1, y_hat.channels(0, c0), out=p.channels(2 * M, 4 * M))
+            for parity in (1, 0):
+                if parity == 0:                    # the group's anchors are in y_hat, its non-anchors still zero
+                    self._ctx_conv(i)(y_hat.channels(c0, c1), out=p.channels(0, 2 * M))
+                gp = self._sub("entropy_parameters", i, p)
+                yield i, c0, c1, parity, gp.channels(0, cg), gp.channels(cg, 2 * cg)
+
+    def _trace_device(self, trace, y_hat, z_hat, x_hat):
+        bounds = ELIC_GROUPS + (self.M,)
+        trace["y_hat"] = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
+        trace["z_hat"] = hip.nhwc_to_nchw(z_hat)
+        trace["x_hat"] = x_hat
+
+    def _compress_device(self, x, waves, trace):
+        L, M = hip.lib(), self.M
+        xt = hip.nchw_to_nhwc(x.contiguous().float())
+        y = self.seq("g_a", xt)
+        z = self.seq("h_a", y)
+        dev, n, h, w = y.buf.device, y.n, y.h, y.w
+        if (h, w) != (4 * z.h, 4 * z.w) or w % 2:
+            raise hip.VcError(f"latent {h}x{w} / hyper-latent {z.h}x{z.w}: the frame must be a multiple of 64")
+        bits = BitCounter(dev, max_rows=11)
+        table = self._scale_table_dev()
+        z_hat = T.empty(n, z.h, z.w, z.c, dev)
+        z_sym = torch.empty((n, z.c * z.h * z.w), dtype=torch.int32, device=dev)
+        hip.check(L.vc_eb_forward(hip.stream(), z.view(), self.entropy_bottleneck.device_params().data_ptr(), None, None,
+                                  z_hat.view(), z_sym.data_ptr(), bits.next_row_ptr(), bits.slots, None), "vc_eb_forward")
+        hyper = self.seq("h_s", z_hat)
+        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
+        z_index = torch.arange(z.c, dtype=torch.int32, device=dev).view(1, z.c, 1).expand(n, z.c, z.h * z.w).reshape(n, -1).contiguous()
+        segments = [(z_sym, z_index, 0)]
+        for i, c0, c1, parity, scales, means in self._device_passes(hyper, y_hat):
+            sym = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
+            idx = torch.empty_like(sym)
+            hip.check(L.vc_gc_forward_ckbd(hip.stream(), y.channels(c0, c1).view(), scales.view(), means.view(), None, None,
+                                           y_hat.channels(c0, c1).view(), parity, bits.next_row_ptr(), bits.slots, sym.data_ptr(),
+                                           idx.data_ptr(), table.data_ptr(), table.numel()), "vc_gc_forward_ckbd")
+            segments.append((sym, idx, 1))
+        x_hat = hip.nhwc_to_nchw(self.seq("g_s", y_hat))
+        total = bits.totals().sum()
+        bounds = ELIC_GROUPS + (M,)
+        groups = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
+        if trace is not None:
+            self._trace_device(trace, y_hat, z_hat, x_hat)
+            trace["coded"] = [(sym, idx) for sym, idx, _ in segments]
+        # the one synchronisation of the pass: the word counts of the payloads, after the last launch
+        payloads = hip.irans_encode(segments, [self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()], waves)
+        return {"strings": payloads, "shape": torch.Size([z.h, z.w]), "y_hat": groups, "x_hat": x_hat, "bits": total, "coder": "device",
+                "waves": int(waves)}
+
+    def _decompress_device(self, strings, shape, waves, trace):
+        M = self.M
+        dev = self.entropy_bottleneck.quantiles.device
+        hz, wz = int(shape[0]), int(shape[1])
+        if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
+            raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
+        uploaded = isinstance(strings, hip.IransDecoder)
+        if not uploaded and not (isinstance(strings, (list, tuple)) and strings and all(isinstance(b, (bytes, bytearray)) for b in strings)):
+            raise hip.VcError('ELIC.decompress(coder="device"): strings is one payload (bytes) per image, as compress(coder="device") '
+                              "returns it -- this looks like the host-coded [[g0, ..., g4], z] lists")
+        dec = strings if uploaded else hip.IransDecoder(strings, waves, dev)
+        if dec.waves != int(waves):
+            raise hip.VcError(f"the uploaded payloads were read with waves {dec.waves}, not {waves}")
+        n, h, w = dec.images, 4 * hz, 4 * wz
+        table = self._scale_table_dev()
+        eb_tables, gc_tables = self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()
+        z_hat = T.empty(n, hz, wz, self.N, dev)
+        dec.decode_eb(eb_tables, self.entropy_bottleneck.device_params(), None, z_hat)
+        hyper = self.seq("h_s", z_hat)
+        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
+        for i, c0, c1, parity, scales, means in self._device_passes(hyper, y_hat):
+            dec.decode_gc_ckbd(gc_tables, scales, means, parity, table, None, y_hat.channels(c0, c1))
+        x_hat = hip.nhwc_to_nchw(self.seq("g_s", y_hat))
+        bounds = ELIC_GROUPS + (M,)
+        groups = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
+        if trace is not None:
+            self._trace_device(trace, y_hat, z_hat, x_hat)
+        if not uploaded:                           # the one read, after everything is enqueued
+            dec.finish()
+        return {"x_hat": x_hat, "y_hat": groups}
+
+    def compress(self, x, coder="host", waves=4, trace=None):
+        """{"strings": [[[g0], [g1], [g2], [g3], [g4]], [z]], "shape", "y_hat": 5 NCHW tensors} like elic.py:307-414.
+
+        ``coder="device"``: "strings" is one payload of the interleaved coder per image (hyper-latent segment, then the ten passes),
+        coded by one vc_irans_encode launch on the integers where they lie; the result gains "x_hat" (the synthesis of the y_hat
+        that was coded), "bits" (0-dim float64 device tensor: -log2 p of the coded symbols), "coder" and "waves".  ``trace``
+        (device coder): receives "coded" (the segment table: (symbols, indexes) of z and of the ten passes), "y_hat", "z_hat",
+        "x_hat".  ``waves`` and ``trace`` belong to the device coder: the host coder ignores the first and refuses the second."""
         _require_frames(x)
+        if coder != "host":
+            self._check_coder(coder, waves)
+            return self._compress_device(x, waves, trace)
+        if trace is not None:
+            raise hip.VcError('ELIC.compress: trace= belongs to coder="device" (the host-coded path returns its latents in "y_hat")')
         L, M = hip.lib(), self.M
         xt = hip.nchw_to_nhwc(x.contiguous().float())
         y = self.seq("g_a", xt)
@@ -909,9 +1030,22 @@ class ELIC(JointAutoregressiveHierarchicalPriors):
         groups = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
         return {"strings": [strings, z_strings], "shape": torch.Size([z.h, z.w]), "y_hat": groups}
 
-    def decompress(self, strings, shape):
-        """{"x_hat", "cost_time", "y_hat"} like elic.py:416-496 (two decode_stream calls per group string)."""
+    def decompress(self, strings, shape, coder="host", waves=4, trace=None):
+        """{"x_hat", "cost_time", "y_hat"} like elic.py:416-496 (two decode_stream calls per group string).
+
+        ``coder="device"`` reads the payloads of ``compress(coder="device")`` (or a hip.IransDecoder that already uploaded them):
+        one upload, then launches only, {"x_hat", "y_hat"}; the decoder's error words are read once at the end (VcError) -- by
+        the caller (``finish()``) when it handed in the uploaded decoder.  ``trace``: receives "y_hat", "z_hat", "x_hat"."""
         import time
+        if coder != "host":
+            self._check_coder(coder, waves)
+            return self._decompress_device(strings, shape, waves, trace)
+        if trace is not None:
+            raise hip.VcError('ELIC.decompress: trace= belongs to coder="device" (the host-coded path returns its latents in "y_hat")')
+        if isinstance(strings, hip.IransDecoder) or len(strings) != 2 or len(strings[0]) != 5 or \
+                not all(isinstance(g, (list, tuple)) for g in list(strings[0]) + [strings[1]]):
+            raise hip.VcError('ELIC.decompress(coder="host"): strings is [[g0, ..., g4], z] with one byte string per image in each list '
+                              '-- pass coder="device" for the payloads of compress(coder="device")')
         t0 = time.process_time()
         L, M = hip.lib(), self.M
         dev = self.entropy_bottleneck.quantiles.device
