@@ -307,6 +307,15 @@ int vc_to_half(vc_stream s, vc_view a, void *out_half);
 int vc_offset_diversity_hxp(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2, vc_view flow2,
                             float magnitude, const float *wpk, const float *bias, int groups, vc_view out);
 int vc_to_half_planar(vc_stream s, vc_view a, int cg, void *out_half);
+/* fp16 path: vc_deform_pair on GROUP-PLANAR half features.  x1 / x2 describe ONE group's plane of a vc_to_half_planar tensor exactly
+ * as for vc_offset_diversity_hxp (c = cg, sw = cg, sh = w * cg, sn = (G/2) * h * w * cg, strides in elements); raw_r, wpk, bias and
+ * out are those of vc_deform_pair (raw_r.c == 27*G/2, offsets as they come, logistic on the mask, no flow).  The gathered values are
+ * the features rounded to half; offsets, modulation, bilinear weights and accumulation stay fp32.  One instance per shape of the
+ * ICIP2023 model and nothing else: (cg, og) one of (4,4) (8,8) (12,12), at most 8 groups per reference (G <= 16), raw tensors that
+ * allow 16-byte record pieces (pointer % 16 == 0, strides % 4 == 0), feature pointers 8-byte aligned, one image of the features
+ * below 4 GiB (32-bit byte offsets).  Everything else -- and every argument vc_deform_pair refuses -- is VC_EINVAL before any launch. */
+int vc_deform_pair_hxp(vc_stream s, vc_view x1, vc_view raw1, vc_view x2, vc_view raw2, const float *wpk, const float *bias,
+                       int groups, vc_view out);
 
 /* Gate of compressai.layers.AttentionBlock (ELIC intra codec of ICIP2024, src/model/elic.py:97-121):
  * out = a * sigmoid(b) + identity. */

@@ -57,7 +57,7 @@ __device__ __forceinline__ float sigmoid_bf(float x)
 //   MODE_GENERIC  offsets and (optional) mask are read as they lie in their tensors (vc_deform_conv2d)
 //   MODE_OD       the raw record of OffsetDiversity: tanh * magnitude + flipped flow, logistic on the mask (vc_offset_diversity*)
 //   MODE_PAIR     the raw record of two plain modulated layers (ICIP2023 DeformB.get_deformed_maps): offsets as they come, logistic
-//                 on the mask, no flow (vc_deform_pair)
+//                 on the mask, no flow (vc_deform_pair; vc_deform_pair_hxp: the XH body on group-planar half features)
 // MODE_OD and MODE_PAIR share the record fetch (FUSED below).
 enum { MODE_GENERIC = 0, MODE_OD = 1, MODE_PAIR = 2 };
 
@@ -427,8 +427,18 @@ template <int CG, int OG, int MODE> int launch(hipStream_t st, const DeformArgs 
         // 12 -> 12 channels per group (ICIP2023 level 3): 144 products per tap and channel next to the gathered values.  The scalar
         // form does not fit the 128 registers a 1024-thread workgroup leaves a lane (the compiler spilled 384 bytes per lane), so
         // this pair exists with the 512-thread bound only -- at most 8 groups per reference, which is the model's shape; the vector
-        // form gathers one tap at a time (TB = 1).  fp32 features only.
-        if (!small || a.x_half) return VC_EINVAL;
+        // form gathers one tap at a time (TB = 1).  fp32 features, with ONE exception: the pair on group-planar half features
+        // (vc_deform_pair_hxp), which keeps no weights in LDS -- the 64 records alone, 54 KiB, no hipFuncSetAttribute.
+        if (!small) return VC_EINVAL;
+        if (a.x_half) {
+            if constexpr (MODE == MODE_PAIR && CG == 12 && OG == 12) {
+                auto ok4 = [&](const vc_view &v) {
+                    return (27 * half) % 4 == 0 && reinterpret_cast<uintptr_t>(v.p) % 16 == 0 && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0;
+                };
+                if (a.x_half == 2 && vec && ok4(a.off1) && ok4(a.off2)) return launch_one(k_deform<12, 12, MODE_PAIR, true, 4, 512, true>);
+            }
+            return VC_EINVAL;
+        }
         if constexpr (FUSED) {
             auto ok = [&](const vc_view &v, int w) {
                 return (27 * half) % w == 0 && reinterpret_cast<uintptr_t>(v.p) % (4 * w) == 0 && v.sn % w == 0 && v.sh % w == 0 && v.sw % w == 0;
@@ -449,6 +459,10 @@ template <int CG, int OG, int MODE> int launch(hipStream_t st, const DeformArgs 
         if (a.x_half) {             // half-precision features: the fast fused instance or nothing
             if constexpr (CG % 4 == 0 && MODE == MODE_OD) {
                 if (vec && small && rv == 4) return launch_one(k_deform<CG, OG, MODE_OD, true, 4, 512, true>);
+            }
+            // the pair: group-planar features only, the two shapes of ICIP2023 below 12 channels per group ((12, 12): above)
+            if constexpr (MODE == MODE_PAIR && CG == OG && (CG == 4 || CG == 8)) {
+                if (a.x_half == 2 && vec && small && rv == 4) return launch_one(k_deform<CG, OG, MODE_PAIR, true, 4, 512, true>);
             }
             return VC_EINVAL;
         }
@@ -609,4 +623,42 @@ extern "C" int vc_deform_pair(vc_stream s, vc_view x1, vc_view raw1, vc_view x2,
     a.bias = bias;
     a.groups = groups;
     return dispatch<MODE_PAIR>(as_stream(s), a, x1.c / half, out.c / groups);
+}
+
+// The same on GROUP-PLANAR half features (fp16 path; the view contract of vc_offset_diversity_hxp: x1 / x2 describe ONE group's plane
+// of a vc_to_half_planar tensor).  One instance per shape of the ICIP2023 model -- k_deform<cg, cg, MODE_PAIR, true, 4, 512, true> for
+// cg = 4, 8, 12 -- and no slower form behind it: whatever that instance does not serve is refused here, before any launch.
+extern "C" int vc_deform_pair_hxp(vc_stream s, vc_view x1, vc_view raw1, vc_view x2, vc_view raw2, const float *wpk, const float *bias,
+                                  int groups, vc_view out)
+{
+    if (!x1.p || !x2.p || !raw1.p || !raw2.p || !wpk || !out.p) return VC_EINVAL;
+    if (groups < 2 || groups % 2 || groups > 16) return VC_EINVAL;          // at most 8 groups per reference
+    const int half = groups / 2;
+    if (x1.c != x2.c || raw1.c != 27 * half || raw2.c != 27 * half || out.c % groups) return VC_EINVAL;
+    const vc_view *vs[] = {&x1, &x2, &raw1, &raw2};
+    for (const vc_view *v : vs)
+        if (v->h != out.h || v->w != out.w || v->n != out.n) return VC_EINVAL;
+    const int cg = x1.c, og = out.c / groups;
+    if (cg != og || (cg != 4 && cg != 8 && cg != 12)) return VC_EINVAL;
+    for (const vc_view *v : {&x1, &x2}) {
+        // dense planes, [n][G/2][h][w][cg]; 8-byte aligned (a group's pixel is 8, 16 or 24 bytes)
+        if (v->sw != v->c || v->sh != (long long)v->w * v->c || v->sn != (long long)half * v->h * v->sh) return VC_EINVAL;
+        if (reinterpret_cast<uintptr_t>(v->p) % 8) return VC_EINVAL;
+        // 32-bit byte offsets inside one image of the features, 24-bit row / pixel multiplies
+        if ((long long)half * v->h * v->sh * 2 >= (1ll << 32) || v->sh * 2 >= (1ll << 24) || v->h >= (1 << 24) || v->w >= (1 << 24)) return VC_EINVAL;
+    }
+    for (const vc_view *v : {&raw1, &raw2})                                  // records in 16-byte pieces (27 * half floats: half % 4 == 0)
+        if ((27 * half) % 4 || reinterpret_cast<uintptr_t>(v->p) % 16 || v->sn % 4 || v->sh % 4 || v->sw % 4) return VC_EINVAL;
+    x1.c *= half, x2.c *= half;
+    DeformArgs a = {};
+    a.x1 = x1;
+    a.x2 = x2;
+    a.off1 = raw1;
+    a.off2 = raw2;
+    a.out = out;
+    a.wpk = wpk;
+    a.bias = bias;
+    a.groups = groups;
+    a.x_half = 2;
+    return dispatch<MODE_PAIR>(as_stream(s), a, cg, og);
 }

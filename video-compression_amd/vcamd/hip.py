@@ -201,6 +201,7 @@ def lib():
     sig("vc_to_half", ci, vp, View, vp)
     sig("vc_offset_diversity_hxp", ci, vp, View, View, View, View, View, View, cf, vp, vp, ci, View)
     sig("vc_to_half_planar", ci, vp, View, ci, vp)
+    sig("vc_deform_pair_hxp", ci, vp, View, View, View, View, vp, vp, ci, View)
     sig("vc_attention_gate", ci, vp, View, View, View, View)
     sig("vc_sse_clamp01", ci, vp, View, View, vp, ci)
     sig("vc_select_flow", ci, vp, vp, ci, ctypes.c_double, ctypes.POINTER(View), View, vp)
@@ -250,7 +251,7 @@ EXPORTED_SYMBOLS = [
     "vc_conv_pack_weights_split", "vc_split3", "vc_split3_pad", "vc_nchw_to_nhwc",
     "vc_nhwc_to_nchw", "vc_u8hwc_to_f32nchw_pad", "vc_f32nchw_to_u8hwc", "vc_avgpool_reflectpad", "vc_maxpool2", "vc_maxpool2_sp3", "vc_avgpool2_sp3", "vc_upsample_bilinear", "vc_upsample_bilinear_sp3", "vc_axpby", "vc_clamp01", "vc_channel_scale", "vc_warp",
     "vc_spynet_preprocess", "vc_spynet_level_input", "vc_spynet_level_input_sp3", "vc_lhbdc_blend", "vc_flex_blend",
-    "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_deform_pair", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar",
+    "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_deform_pair", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar", "vc_deform_pair_hxp",
     "vc_attention_gate", "vc_sse_clamp01", "vc_select_flow", "vc_eb_forward", "vc_eb_dequant", "vc_gc_forward", "vc_gc_indexes", "vc_refine_scales",
     "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_gc_forward_ckbd", "vc_gc_indexes_ckbd", "vc_gc_dequant_ckbd", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
@@ -436,6 +437,10 @@ FUSE_TAIL = bool(int(os.environ.get("VC_FUSE_TAIL", "1")))
 # weights and accumulation stay fp32.  VC_HALF_DEFORM=0 gathers fp32 features (A/B, tests).
 HALF_DEFORM = bool(int(os.environ.get("VC_HALF_DEFORM", "1")))
 HALF_DEFORM_PLANAR = bool(int(os.environ.get("VC_HALF_DEFORM_PLANAR", "1")))   # group-planar half features under the deformable gathers
+# fp16 path only: the deformable pairs of ICIP2023 (PackedDeform.pair) gather from group-planar half copies of the two references
+# too (vc_deform_pair_hxp; needs HALF_DEFORM and HALF_DEFORM_PLANAR).  VC_HALF_DEFORM_PAIR=0 keeps the fp32 vc_deform_pair in
+# fp16 mode (A/B, tests); the measurement behind the default is in DESIGN.md 4f.
+HALF_DEFORM_PAIR = bool(int(os.environ.get("VC_HALF_DEFORM_PAIR", "1")))
 # Bitstream paths (compress / decompress): scales within SCALE_REFINE_EPS (relative) of a scale-table entry are recomputed in fp64
 # from the last hyper-synthesis layer's input (vc_refine_scales): this side's table indexes stop depending on its summation order.
 # VC_SCALE_REFINE=0 keeps the plain fp32 scales (A/B, tests).
@@ -1095,20 +1100,37 @@ class PackedDeform:
         return None if self.bias is None else self.bias.data_ptr()
 
     def pair(self, x1, raw1, x2, raw2, out=None):
-        """vc_deform_pair: ICIP2023 DeformB.get_deformed_maps in one launch (fp32 features)."""
+        """vc_deform_pair: ICIP2023 DeformB.get_deformed_maps in one launch (fp32 features in; on the fp16 path the kernel gathers
+        from group-planar half copies made here, vc_deform_pair_hxp)."""
         if x1.dtype != "f32" or x2.dtype != "f32":
             raise VcError("vc_deform_pair reads fp32 features")
         if out is None:
             out = T.empty(x1.n, x1.h, x1.w, self.cout, x1.buf.device)
+        cg, og = self.cin // self.groups, self.cout // self.groups
+        # the half-feature entry has one instance per shape of the model (csrc/deform.hip: (4, 4), (8, 8), (12, 12), <= 8 groups per
+        # reference, records in 16-byte pieces); the alignment conditions are those of offset_diversity below
+        planar = (_PRECISION == "fp16" and HALF_DEFORM and HALF_DEFORM_PLANAR and HALF_DEFORM_PAIR and cg == og and cg in (4, 8, 12)
+                  and self.groups <= 16 and raw1.c % 4 == 0 and raw2.c % 4 == 0
+                  and all(t.ptr % 16 == 0 and t.sw % 4 == 0 and t.sh % 4 == 0 and t.sn % 4 == 0 and t.c % 4 == 0 for t in (x1, x2))
+                  and all(t.ptr % 16 == 0 and t.sw % 4 == 0 and t.sh % 4 == 0 and t.sn % 4 == 0 for t in (raw1, raw2)))
+        if planar:
+            n_, h_, w_, hg = x1.n, x1.h, x1.w, self.groups // 2
+            p1, p2 = to_half_planar(x1, cg), to_half_planar(x2, cg)
+            v1 = View(p1.ptr, n_, h_, w_, cg, hg * h_ * w_ * cg, w_ * cg, cg)
+            v2 = View(p2.ptr, n_, h_, w_, cg, hg * h_ * w_ * cg, w_ * cg, cg)
 
         def launch():
-            check(lib().vc_deform_pair(stream(), x1.view(), raw1.view(), x2.view(), raw2.view(), self.wpk.data_ptr(), self._bias_ptr(),
-                                       self.groups, out.view()), "vc_deform_pair")
+            if planar:
+                check(lib().vc_deform_pair_hxp(stream(), v1, raw1.view(), v2, raw2.view(), self.wpk.data_ptr(), self._bias_ptr(),
+                                               self.groups, out.view()), "vc_deform_pair_hxp")
+            else:
+                check(lib().vc_deform_pair(stream(), x1.view(), raw1.view(), x2.view(), raw2.view(), self.wpk.data_ptr(), self._bias_ptr(),
+                                           self.groups, out.view()), "vc_deform_pair")
         if timer is None:
             launch()
         else:
             flops = 2.0 * x1.n * x1.h * x1.w * self.cout * (self.cin // self.groups) * 9
-            nbytes = x1.n * x1.h * x1.w * 4.0 * (self.cin + raw1.c + raw2.c + self.cout)
+            nbytes = x1.n * x1.h * x1.w * ((2.0 if planar else 4.0) * self.cin + 4.0 * (raw1.c + raw2.c + self.cout))
             timer.bracket(f"deform pair k3 {self.cin}->{self.cout} g{self.groups} @{x1.n}x{x1.h}x{x1.w}", flops, launch, nbytes)
         return out
 

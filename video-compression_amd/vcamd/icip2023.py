@@ -12,7 +12,8 @@ level whose outputs are concatenated.  Every class here is the ICIP2024 class bu
 keys are the reference's (1034 entries, tests/golden/icip2023_state_schema.txt).
 
 Per level the two deformable layers run as ONE launch (vc_deform_pair: a grouped deformable convolution of 16 groups, groups 0..7
-on fref1 with the first layer's weights, 8..15 on fref2 with the second's; offsets used as they come, logistic on the mask).
+on fref1 with the first layer's weights, 8..15 on fref2 with the second's; offsets used as they come, logistic on the mask; in fp16
+mode on group-planar half copies of the two references, vc_deform_pair_hxp -- hip.HALF_DEFORM_PAIR).
 Per level one buffer [fref1 | fref2 | fcur] holds what the reference concatenates: f_inp is the buffer, f_cond_inp its first two
 thirds, so no concatenation is launched.  The reference has no compress() for this model; compress / decompress here are the
 twelve strings per frame of FlowGuidedB's format (vcamd/icip2024.py: _Elic.compress_t / decompress_t), without a container.
