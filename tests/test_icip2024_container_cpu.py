@@ -1,4 +1,4 @@
-"""The ICIP2024 B-frame container (vcamd/bitstream.py: pack_icip2024_frame / unpack_icip2024_frame) on synthetic strings:
+"""The ICIP2024 B-frame container (vcamd/containers.py: pack_icip2024_frame / unpack_icip2024_frame) on synthetic strings:
 round trip, the header layout INTEGRATION.md states, and the refusals of a reader that trusts nothing in the buffer."""
 import os
 import re
@@ -7,7 +7,7 @@ import struct
 import numpy as np
 import pytest
 
-from vcamd import bitstream, hip
+from vcamd import containers, hip
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -25,29 +25,29 @@ def _strings(seed, empty=()):
 def _pack(strings, **kw):
     args = dict(shape=(17, 30), down_ratio=4, s=1.5, scale1=0.75, scale2=0.25)
     args.update(kw)
-    return bitstream.pack_icip2024_frame(strings, **args)
+    return containers.pack_icip2024_frame(strings, **args)
 
 
 @pytest.mark.parametrize("empty", [(), (("offset", "z"),), (("residual", 4), ("offset", 0)),
                                    tuple((c, k) for c in ("offset", "residual") for k in ("z", 0, 1, 2, 3, 4))])
 def test_round_trip(empty):
     strings = _strings(3, empty)
-    got = bitstream.unpack_icip2024_frame(_pack(strings))
+    got = containers.unpack_icip2024_frame(_pack(strings))
     assert got["strings"] == strings
     assert got["shape"] == (17, 30) and got["down_ratio"] == 4
     assert (got["s"], got["scale1"], got["scale2"]) == (1.5, 0.75, 0.25)
 
 
 def test_numbers_are_stored_as_fp32():
-    got = bitstream.unpack_icip2024_frame(_pack(_strings(1), s=1.3, scale1=0.67, scale2=0.33))
+    got = containers.unpack_icip2024_frame(_pack(_strings(1), s=1.3, scale1=0.67, scale2=0.33))
     assert (got["s"], got["scale1"], got["scale2"]) == tuple(float(np.float32(v)) for v in (1.3, 0.67, 0.33))
 
 
 def test_picks_the_image_of_a_batch():
     a, b = _strings(5), _strings(6)
     both = {c: [[a[c][0][i] + b[c][0][i] for i in range(5)], a[c][1] + b[c][1]] for c in a}
-    assert bitstream.unpack_icip2024_frame(_pack(both, image=0))["strings"] == a
-    assert bitstream.unpack_icip2024_frame(_pack(both, image=1))["strings"] == b
+    assert containers.unpack_icip2024_frame(_pack(both, image=0))["strings"] == a
+    assert containers.unpack_icip2024_frame(_pack(both, image=1))["strings"] == b
 
 
 def test_header_layout_is_the_documented_one():
@@ -70,7 +70,7 @@ def test_header_layout_is_the_documented_one():
 
 def test_reader_refuses_what_it_cannot_trust():
     data = _pack(_strings(9))
-    bitstream.unpack_icip2024_frame(data)
+    containers.unpack_icip2024_frame(data)
     bad = {
         "magic": b"VCIX" + data[4:],
         "version": data[:4] + bytes([2]) + data[5:],
@@ -85,7 +85,7 @@ def test_reader_refuses_what_it_cannot_trust():
     }
     for what, buf in bad.items():
         with pytest.raises(hip.VcError):
-            bitstream.unpack_icip2024_frame(buf)
+            containers.unpack_icip2024_frame(buf)
             pytest.fail(f"{what}: accepted")
 
 

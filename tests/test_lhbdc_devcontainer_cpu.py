@@ -1,4 +1,4 @@
-"""The VCLD container of the LHBDC stream codec's coder="device" (vcamd/bitstream.py: pack_lhbdc_frame_dev /
+"""The VCLD container of the LHBDC stream codec's coder="device" (vcamd/containers.py: pack_lhbdc_frame_dev /
 unpack_lhbdc_frame_dev) and the two-segment payload it carries, through the host reference of the
 interleaved coder -- no GPU.
 
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from test_irans_cpu import MEASURED_RATIO, SEQUENTIAL_BYTES, _gaussian_tables, draw, make_set
-from vcamd import bitstream, hip
+from vcamd import containers, hip
 
 H, W = 192, 256                        # the frame of tests/test_stream_gpu.py: hyper-latents 1x1 (motion) and 3x4 (residual)
 MV_SHAPE, RES_SHAPE = (1, 1), (3, 4)
@@ -27,25 +27,25 @@ def _payload(waves, seed=0, words=40):
 def test_round_trip():
     for waves in (1, 2, 4, 8, 16):
         mv, res = _payload(waves, 1, 10), _payload(waves, 2, 77)
-        blob = bitstream.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, waves, mv, res)
+        blob = containers.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, waves, mv, res)
         assert blob[:4] == b"VCLD" and len(blob) == 26 + len(mv) + len(res)
-        got = bitstream.unpack_lhbdc_frame_dev(blob, H, W)
+        got = containers.unpack_lhbdc_frame_dev(blob, H, W)
         assert got == {"lmbda": 1626, "waves": waves, "mv_shape": MV_SHAPE, "res_shape": RES_SHAPE, "mv": mv, "res": res}
     for bad_waves in (0, 3, 32):
         with pytest.raises(hip.VcError):
-            bitstream.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, bad_waves, mv, res)
+            containers.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, bad_waves, mv, res)
     with pytest.raises(hip.VcError):
-        bitstream.pack_lhbdc_frame_dev(1626, (0, 1), RES_SHAPE, 4, mv, res)
+        containers.pack_lhbdc_frame_dev(1626, (0, 1), RES_SHAPE, 4, mv, res)
 
 
 def test_refusals():
     mv, res = _payload(4, 3), _payload(4, 4)
-    good = bitstream.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, 4, mv, res)
-    bitstream.unpack_lhbdc_frame_dev(good, H, W)
+    good = containers.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, 4, mv, res)
+    containers.unpack_lhbdc_frame_dev(good, H, W)
 
     def refused(blob, h=H, w=W):
         with pytest.raises(hip.VcError):
-            bitstream.unpack_lhbdc_frame_dev(blob, h, w)
+            containers.unpack_lhbdc_frame_dev(blob, h, w)
 
     refused(b"VCLX" + good[4:])                                        # magic
     refused(b"VCIB" + good[4:])
@@ -100,8 +100,8 @@ def test_segment_layout_through_the_host_reference(waves):
         got = hip.irans_decode_host(payload, [(idx, k) for _, idx, k in segs], [eb, gc], waves)
         for (sym, _, _), g in zip(segs, got):
             assert np.array_equal(g, sym)
-        blob = bitstream.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, waves, payload, payload)
-        assert bitstream.unpack_lhbdc_frame_dev(blob, H, W)["res"] == payload
+        blob = containers.pack_lhbdc_frame_dev(1626, MV_SHAPE, RES_SHAPE, waves, payload, payload)
+        assert containers.unpack_lhbdc_frame_dev(blob, H, W)["res"] == payload
         # the segments are not interchangeable: decoding them in the other order is refused or gives other integers
         try:
             other = hip.irans_decode_host(payload, [(segs[1][1], 1), (segs[0][1], 0)], [eb, gc], waves)

@@ -25,25 +25,25 @@ so a GOP decodes as uploads, then launches only, then one read of the error word
 Flex-Rate is not offered here on purpose: its compress() codes the UN-gained latent while forward() quantises the gained
 one (quirk B.6), so the reference's own encoder and decoder disagree on the reconstruction whenever the gain differs from
 one -- there is no closed loop to pipeline.
+
+This module is the GPU pipeline only (streams, events, the thread pool, launch order); the bytes of ``bits_B.bin``, ``VCLD`` and the
+other containers are written and read in containers.py.
 """
-import struct
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from . import hip
+# the byte formats live in containers.py; their names stay importable from here
+from .containers import (ICIP2024_DEV_MAGIC, ICIP2024_DEV_TAIL, ICIP2024_DOWN_RATIOS, ICIP2024_HEADER, ICIP2024_INTRA_HEADER,  # noqa: F401
+                         ICIP2024_INTRA_MAGIC, ICIP2024_INTRA_VERSION, ICIP2024_LENGTHS, ICIP2024_MAGIC, ICIP2024_VERSION, LHBDC_DEV_HEADER,
+                         LHBDC_DEV_MAGIC, LHBDC_DEV_VERSION, SEQUENCE_FAMILY_ICIP2024, SEQUENCE_HEADER, SEQUENCE_MAGIC, SEQUENCE_RECORD,
+                         SEQUENCE_TYPES, SEQUENCE_VERSION, finish_all, pack_bits_b, pack_icip2024_frame, pack_icip2024_frame_dev,
+                         pack_icip2024_intra_dev, pack_lhbdc_frame_dev, pack_sequence, sequence_plan, unpack_icip2024_frame,
+                         unpack_icip2024_frame_dev, unpack_icip2024_intra_dev, unpack_lhbdc_frame_dev, unpack_sequence)
 from .gop import DECODING_INFO, LEVEL_GROUPS
-from .hip import T
-from .lhbdc import Model, _cli_predictors, _count, check_container_shapes, frame_list, read_container
-
-
-def _pack_container(lmbda, mv_shape, res_shape, mv_y, mv_z, res_y, res_z):
-    """bits_B.bin (encode_B.py:114-126); see lhbdc.write_container."""
-    head = (np.array(lmbda, dtype=np.uint32).tobytes() + np.array(tuple(mv_shape), dtype=np.uint16).tobytes() +
-            np.array(len(mv_y), dtype=np.uint32).tobytes() + np.array(len(mv_z), dtype=np.uint32).tobytes() +
-            np.array(tuple(res_shape), dtype=np.uint16).tobytes() + np.array(len(res_y), dtype=np.uint32).tobytes())
-    return head + mv_y + mv_z + res_y + res_z
+from .lhbdc import Model, _cli_predictors, _count, _motion_difference, check_container_shapes, frame_list, read_container
 
 
 class _Tables:
@@ -72,7 +72,7 @@ class PendingContainers:
 
 class LhbdcStreamCodec:
     """``coder="host"`` (default): bits_B.bin containers, the host range coder on worker threads, as described above.
-    ``coder="device"``: VCLD containers (below) coded and decoded by the interleaved range coder's kernels -- the same integers,
+    ``coder="device"``: VCLD containers (containers.py) coded and decoded by the interleaved range coder's kernels -- the same integers,
     the same reconstructions; ``waves`` sub-streams per payload on the encoder (the decoder takes the count from the container).
     The worker pool is not created: nothing is coded on the host."""
     CODERS = ("host", "device")
@@ -107,28 +107,30 @@ class LhbdcStreamCodec:
         return host, done
 
     # -- encoder ------------------------------------------------------------------------------------------
+    def _encode_level(self, x_before, x_current, x_after, hand_over):
+        """The launches of one encoded level, whichever coder takes the integers: ``hand_over(codec, sym)`` is called right behind
+        each compressor's code_t -- the motion integers leave before the NHWC conversion and the prediction are enqueued, the
+        residual's before the final addition.  Returns (x_hat NCHW, n, (mv_sym, res_sym), what the two calls returned)."""
+        m = self.model
+        xb_, xc_, xa_ = (frame_list(t) for t in (x_before, x_current, x_after))      # tensors or lists of frames
+        n, dev = _count(xc_), xc_[0].device
+        diff, flow_ba, flow_ab, hh, ww = _motion_difference(m, {"b": xb_, "c": xc_, "a": xa_}, n, dev)
+        mv_hat, mv_sym = m.mv_compressor.code_t(diff)
+        handed_mv = hand_over(m.mv_compressor, mv_sym)
+        xb, xc, xa = hip.nchw_frames_to_nhwc(xb_), hip.nchw_frames_to_nhwc(xc_), hip.nchw_frames_to_nhwc(xa_)
+        pred, resid = m._predict(xb, xa, mv_hat, flow_ab, flow_ba, hh, ww, cur=xc)
+        res_hat, res_sym = m.residual_compressor.code_t(resid)
+        handed_res = hand_over(m.residual_compressor, res_sym)
+        x_hat = hip.nhwc_to_nchw(hip.axpby(res_hat, pred))
+        return x_hat, n, (mv_sym, res_sym), (handed_mv, handed_res)
+
     def encode_frames(self, x_before, x_current, x_after):
         """n independent B-frames (one hierarchy level).  Returns (x_hat NCHW = what decode_frames will output,
         PendingContainers).  No host synchronisation: the caller can enqueue the next level at once."""
         if self.coder == "device":
             return self._encode_frames_dev(x_before, x_current, x_after)
-        m = self.model
-        xb_, xc_, xa_ = (frame_list(t) for t in (x_before, x_current, x_after))      # tensors or lists of frames
-        n, dev = _count(xc_), xc_[0].device
-        frames = {"b": xb_, "c": xc_, "a": xa_}
-        flow_ba, flow_ab, hh, ww = _cli_predictors(m, frames, n)
-        cur = m._flows(frames, [("c", "b"), ("c", "a")])
-        cur_flows, _, _ = Model._pool_pad(cur, 1.0)
-        diff = T.empty(n, flow_ab.h, flow_ab.w, 4, dev)
-        hip.axpby(cur_flows.images(0, n), flow_ab, 1.0, -1.0, out=diff.channels(0, 2))
-        hip.axpby(cur_flows.images(n, 2 * n), flow_ba, 1.0, -1.0, out=diff.channels(2, 4))
-        mv_hat, mv_sym = m.mv_compressor.code_t(diff)
-        host_mv, ev_mv = self._to_host_async([mv_sym["y_sym"], mv_sym["y_idx"], mv_sym["z_sym"]])
-        xb, xc, xa = hip.nchw_frames_to_nhwc(xb_), hip.nchw_frames_to_nhwc(xc_), hip.nchw_frames_to_nhwc(xa_)
-        pred, resid = m._predict(xb, xa, mv_hat, flow_ab, flow_ba, hh, ww, cur=xc)
-        res_hat, res_sym = m.residual_compressor.code_t(resid)
-        host_res, ev_res = self._to_host_async([res_sym["y_sym"], res_sym["y_idx"], res_sym["z_sym"]])
-        x_hat = hip.nhwc_to_nchw(hip.axpby(res_hat, pred))
+        x_hat, n, (mv_sym, res_sym), ((host_mv, ev_mv), (host_res, ev_res)) = self._encode_level(
+            x_before, x_current, x_after, lambda codec, sym: self._to_host_async([sym["y_sym"], sym["y_idx"], sym["z_sym"]]))
         mv_shape, res_shape = mv_sym["shape"], res_sym["shape"]
         zi_mv, zi_res = self.t_mv.z_index(*mv_shape), self.t_res.z_index(*res_shape)
 
@@ -141,7 +143,7 @@ class LhbdcStreamCodec:
             y, idx, z = (h.numpy() for h in host_res)
             res_z = hip.rans_encode(z[i], zi_res, *self.t_res.eb)
             res_y = hip.rans_encode(y[i], idx[i], *self.t_res.gc)
-            return _pack_container(self.lmbda, mv_shape, res_shape, mv_y, mv_z, res_y, res_z)
+            return pack_bits_b(self.lmbda, mv_shape, res_shape, mv_y, mv_z, res_y, res_z)
 
         futures = [self.pool.submit(code_one, i) for i in range(n)]
         return x_hat, PendingContainers(futures, (mv_sym, res_sym, host_mv, host_res))
@@ -198,26 +200,11 @@ class LhbdcStreamCodec:
         """encode_frames with the integers coded where they lie: per compressor one vc_irans_encode launch over two segments (z with
         the factorised tables, y with the Gaussian ones) on the tensors of code_t.  Nothing is read back here: the one host
         synchronisation of the level, the read of both compressors' word counts, happens in ``PendingDevContainers.result()``."""
-        m = self.model
-        xb_, xc_, xa_ = (frame_list(t) for t in (x_before, x_current, x_after))
-        n, dev = _count(xc_), xc_[0].device
-        frames = {"b": xb_, "c": xc_, "a": xa_}
-        flow_ba, flow_ab, hh, ww = _cli_predictors(m, frames, n)
-        cur = m._flows(frames, [("c", "b"), ("c", "a")])
-        cur_flows, _, _ = Model._pool_pad(cur, 1.0)
-        diff = T.empty(n, flow_ab.h, flow_ab.w, 4, dev)
-        hip.axpby(cur_flows.images(0, n), flow_ab, 1.0, -1.0, out=diff.channels(0, 2))
-        hip.axpby(cur_flows.images(n, 2 * n), flow_ba, 1.0, -1.0, out=diff.channels(2, 4))
-        mv_hat, mv_sym = m.mv_compressor.code_t(diff)
-        job_mv = self._encode_job(m.mv_compressor, mv_sym, n, dev)
-        xb, xc, xa = hip.nchw_frames_to_nhwc(xb_), hip.nchw_frames_to_nhwc(xc_), hip.nchw_frames_to_nhwc(xa_)
-        pred, resid = m._predict(xb, xa, mv_hat, flow_ab, flow_ba, hh, ww, cur=xc)
-        res_hat, res_sym = m.residual_compressor.code_t(resid)
-        job_res = self._encode_job(m.residual_compressor, res_sym, n, dev)
-        x_hat = hip.nhwc_to_nchw(hip.axpby(res_hat, pred))
-        return x_hat, PendingDevContainers([job_mv, job_res], self.lmbda, mv_sym["shape"], res_sym["shape"], self.waves, (mv_sym, res_sym))
+        x_hat, _, (mv_sym, res_sym), jobs = self._encode_level(x_before, x_current, x_after, self._encode_job)
+        return x_hat, PendingDevContainers(list(jobs), self.lmbda, mv_sym["shape"], res_sym["shape"], self.waves, (mv_sym, res_sym))
 
-    def _encode_job(self, codec, sym, n, dev):
+    def _encode_job(self, codec, sym):
+        n, dev = sym["z_sym"].shape[0], sym["z_sym"].device
         segments = [(sym["z_sym"], codec.z_index_dev(n, sym["shape"], dev), 0), (sym["y_sym"], sym["y_idx"], 1)]
         return hip.irans_encode_launch(segments, [codec.entropy_bottleneck.irans_tables(), codec.gaussian_conditional.irans_tables()], self.waves)
 
@@ -264,19 +251,15 @@ class LhbdcStreamCodec:
     def encode_gop(self, gop, dec_first, dec_last):
         """``gop``: 9 padded NCHW frames.  Returns ({order: container bytes}, {order: reconstruction}).  The host coding of
         level l runs while the GPU codes level l+1; the only synchronisation is the final collection."""
-        decoded, pending = {0: dec_first, 8: dec_last}, []
-        for group in LEVEL_GROUPS:
-            xb = [decoded[DECODING_INFO[o][0]] for o in group]
-            xc = [gop[o] for o in group]
-            xa = [decoded[DECODING_INFO[o][1]] for o in group]
-            x_hat, pend = self.encode_frames(xb, xc, xa)
-            for i, o in enumerate(group):
-                decoded[o] = x_hat[i:i + 1]
-            pending.append((group, pend))
-        containers = {}
-        for group, pend in pending:
-            for o, c in zip(group, pend.result()):
-                containers[o] = c
+        pending = []
+
+        def level(k, group, xb, xa):
+            x_hat, pend = self.encode_frames(xb, [gop[o] for o in group], xa)
+            pending.append(pend)
+            return x_hat
+
+        decoded = _walk_gop(dec_first, dec_last, level)
+        containers = {o: c for group, pend in zip(LEVEL_GROUPS, pending) for o, c in zip(group, pend.result())}
         return containers, decoded
 
     def decode_gop(self, containers, dec_first, dec_last, finish=True):
@@ -287,85 +270,32 @@ class LhbdcStreamCodec:
         (``UploadedGop.finish``)."""
         if self.coder == "device":
             up = containers if isinstance(containers, UploadedGop) else self.upload_gop(containers, dec_first)
-            decoded = {0: dec_first, 8: dec_last}
-            for group, level in zip(LEVEL_GROUPS, up.levels):
-                xb = [decoded[DECODING_INFO[o][0]] for o in group]
-                xa = [decoded[DECODING_INFO[o][1]] for o in group]
-                x_hat = self._decode_level_dev(xb, xa, level)
-                for i, o in enumerate(group):
-                    decoded[o] = x_hat[i:i + 1]
+            decoded = _walk_gop(dec_first, dec_last, lambda k, group, xb, xa: self._decode_level_dev(xb, xa, up.levels[k]))
             if finish:
                 up.finish()
             return decoded
-        decoded = {0: dec_first, 8: dec_last}
-        for group in LEVEL_GROUPS:
-            xb = [decoded[DECODING_INFO[o][0]] for o in group]
-            xa = [decoded[DECODING_INFO[o][1]] for o in group]
-            x_hat = self.decode_frames(xb, xa, [containers[o] for o in group])
-            for i, o in enumerate(group):
-                decoded[o] = x_hat[i:i + 1]
-        return decoded
+        return _walk_gop(dec_first, dec_last, lambda k, group, xb, xa: self.decode_frames(xb, xa, [containers[o] for o in group]))
 
     def close(self):
         if self.pool is not None:
             self.pool.shutdown(wait=True)
 
 
-# ------------------------------------------------------------------------------------------------
-# Device-coded LHBDC B-frame container (this project's own format; bits_B.bin stays the default and the reference's)
-# ------------------------------------------------------------------------------------------------
-# One byte string per coded frame, little-endian:
-#   offset  0  4 bytes  magic "VCLD"
-#           4  u8       version (1)
-#           5  u8       waves W (1, 2, 4, 8 or 16): sub-streams per payload
-#           6  u32      lambda (as bits_B.bin)
-#          10  u16 x 2  hyper-latent shape (h, w) of the motion compressor
-#          14  u16 x 2  hyper-latent shape (h, w) of the residual compressor
-#          18  u32 x 2  payload lengths: motion, residual
-#          26  the two payloads in that order
-# A payload is one interleaved-rANS payload (include/vc_hip.h: "Interleaved range coder") of two segments, states and cursors
-# continuing from the first to the second: the hyper-latent z (table set 0 = the factorised tables, index of symbol i =
-# i / (hz * wz), its channel), then the latent y (table set 1 = the Gaussian tables, index from the scales); symbol order = the int32
-# tensors of MeanScaleHyperprior.code_t (NCHW raster).
-LHBDC_DEV_MAGIC = b"VCLD"
-LHBDC_DEV_VERSION = 1
-LHBDC_DEV_HEADER = struct.Struct("<4sBBIHHHHII")
+def _walk_gop(dec_first, dec_last, code_level):
+    """The hierarchy of a GOP-8, level by level: ``code_level(k, group, xb, xa)`` gets the display orders of level k and the decoded
+    reference frames in front of and behind each of them and returns their reconstructions [len(group), 3, H, W], which the levels
+    below then reference.  Returns {order: reconstruction}, the two boundary frames included."""
+    decoded = {0: dec_first, 8: dec_last}
+    for k, group in enumerate(LEVEL_GROUPS):
+        xb = [decoded[DECODING_INFO[o][0]] for o in group]
+        xa = [decoded[DECODING_INFO[o][1]] for o in group]
+        x_hat = code_level(k, group, xb, xa)
+        for i, o in enumerate(group):
+            decoded[o] = x_hat[i:i + 1]
+    return decoded
+
+
 _FORMATS = {"host": "bits_B.bin", "device": "VCLD"}
-
-
-def pack_lhbdc_frame_dev(lmbda, mv_shape, res_shape, waves, mv_payload, res_payload):
-    """The VCLD container of one frame from the two payloads of ``LhbdcStreamCodec(coder="device")``."""
-    shapes = tuple(int(v) for v in tuple(mv_shape) + tuple(res_shape))
-    if len(shapes) != 4 or not all(1 <= v <= 0xffff for v in shapes) or not hip.irans_waves_ok(waves) or not 0 <= int(lmbda) <= 0xffffffff:
-        raise hip.VcError(f"lambda {lmbda} / hyper-latent shapes {shapes} / waves {waves} do not fit the container")
-    mv_payload, res_payload = bytes(mv_payload), bytes(res_payload)
-    if max(len(mv_payload), len(res_payload)) > 0xffffffff:
-        raise hip.VcError("a payload is longer than the container's 32-bit length field")
-    return LHBDC_DEV_HEADER.pack(LHBDC_DEV_MAGIC, LHBDC_DEV_VERSION, int(waves), int(lmbda), *shapes, len(mv_payload),
-                                 len(res_payload)) + mv_payload + res_payload
-
-
-def unpack_lhbdc_frame_dev(data, h, w):
-    """Inverse of :func:`pack_lhbdc_frame_dev` for a (padded) h x w frame: ``{"lmbda", "waves", "mv_shape", "res_shape", "mv", "res"}``.
-    Magic, version, wave count, the lengths against the data (no trailing bytes, whole words, at least the W sub-stream headers)
-    and the shapes against the frame size (lhbdc.check_container_shapes) are validated before anything is returned, so before
-    anything is allocated from the header (VcError)."""
-    data = bytes(data)
-    if len(data) < LHBDC_DEV_HEADER.size:
-        raise hip.VcError(f"VCLD container: {len(data)} bytes is shorter than the {LHBDC_DEV_HEADER.size}-byte header")
-    magic, version, waves, lmbda, mh, mw, rh, rw, n_mv, n_res = LHBDC_DEV_HEADER.unpack_from(data, 0)
-    if magic != LHBDC_DEV_MAGIC:
-        raise hip.VcError(f"VCLD container: magic {magic!r} is not {LHBDC_DEV_MAGIC!r}")
-    if version != LHBDC_DEV_VERSION:
-        raise hip.VcError(f"VCLD container: version {version} (this reader knows {LHBDC_DEV_VERSION})")
-    if not hip.irans_waves_ok(waves):
-        raise hip.VcError(f"VCLD container: waves {waves} is not a power of two in 1..16")
-    fixed = LHBDC_DEV_HEADER.size
-    if fixed + n_mv + n_res != len(data) or min(n_mv, n_res) < waves * hip.IRANS_SUBSTREAM_HEADER or n_mv % 4 or n_res % 4:
-        raise hip.VcError(f"VCLD container: payload lengths {n_mv} + {n_res} do not fit {len(data)} bytes / {waves} waves")
-    check_container_shapes((mh, mw), (rh, rw), h, w)
-    return {"lmbda": lmbda, "waves": waves, "mv_shape": (mh, mw), "res_shape": (rh, rw), "mv": data[fixed:fixed + n_mv],
-            "res": data[fixed + n_mv:]}
 
 
 def _refuse_container_of_other_coder(containers, coder):
@@ -403,14 +333,7 @@ class UploadedLevel:
 
     def finish(self):
         """the one read per decoder: VcError when a payload was corrupt (every decoder is read before the first error is raised)"""
-        errors = []
-        for d in (self.mv, self.res):
-            try:
-                d.finish()
-            except hip.VcError as e:
-                errors.append(e)
-        if errors:
-            raise errors[0]
+        finish_all((self.mv, self.res))
 
 
 class UploadedGop:
@@ -418,268 +341,4 @@ class UploadedGop:
         self.levels = levels
 
     def finish(self):
-        errors = []
-        for level in self.levels:
-            try:
-                level.finish()
-            except hip.VcError as e:
-                errors.append(e)
-        if errors:
-            raise errors[0]
-
-
-# ------------------------------------------------------------------------------------------------
-# ICIP2024 B-frame container (this project's own format: the reference has no bitstream for FlowGuidedB)
-# ------------------------------------------------------------------------------------------------
-# One byte string per coded frame, little-endian:
-#   offset  0  4 bytes  magic "VCIB"
-#           4  u8       version (1)
-#           5  u8       down_ratio (1, 2, 4, 8 or 16)
-#           6  u16 x 2  hyper-latent shape (h, w) = frame / 64
-#          10  f32 x 3  s (quality level), scale1, scale2 (both after FlowGuidedB.convert_scales)
-#          22  u32 x 12 string lengths: offset z, offset g0..g4, residual z, residual g0..g4
-#          70  the twelve payloads in that order
-ICIP2024_MAGIC = b"VCIB"
-ICIP2024_VERSION = 1
-ICIP2024_HEADER = struct.Struct("<4sBBHHfff")
-ICIP2024_LENGTHS = struct.Struct("<12I")
-ICIP2024_DOWN_RATIOS = (1, 2, 4, 8, 16)
-
-
-def _icip2024_payloads(strings, image):
-    out = []
-    for codec in ("offset", "residual"):
-        groups, z = strings[codec]
-        if len(groups) != 5:
-            raise hip.VcError(f"{codec}: five group strings per image, got {len(groups)}")
-        out.append(z[image])
-        out.extend(g[image] for g in groups)
-    return [bytes(b) for b in out]
-
-
-def pack_icip2024_frame(strings, shape, down_ratio, s, scale1, scale2, image=0):
-    """The container of image ``image`` of a FlowGuidedB.compress result: ``strings`` / ``shape`` / ``down_ratio`` as it returns
-    them, ``s`` the quality level and ``scale1`` / ``scale2`` the converted scales (FlowGuidedB.convert_scales) it was called
-    with.  The three numbers are stored as fp32 -- compress() and decompress() round the level to fp32 themselves and the
-    converted scales are fp32 values, so a decoder fed from the container uses the encoder's numbers."""
-    hz, wz = int(shape[0]), int(shape[1])
-    if int(down_ratio) not in ICIP2024_DOWN_RATIOS or not (1 <= hz <= 0xffff and 1 <= wz <= 0xffff):
-        raise hip.VcError(f"down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} do not fit the container")
-    payloads = _icip2024_payloads(strings, image)
-    if any(len(p) > 0xffffffff for p in payloads):
-        raise hip.VcError("a string is longer than the container's 32-bit length field")
-    head = ICIP2024_HEADER.pack(ICIP2024_MAGIC, ICIP2024_VERSION, int(down_ratio), hz, wz, float(s), float(scale1), float(scale2))
-    return head + ICIP2024_LENGTHS.pack(*(len(p) for p in payloads)) + b"".join(payloads)
-
-
-def unpack_icip2024_frame(data):
-    """Inverse of :func:`pack_icip2024_frame`: ``{"strings" (one image per list), "shape", "down_ratio", "s", "scale1", "scale2"}``.
-    Magic, version, field ranges and the total length are validated before anything is returned (VcError)."""
-    data = bytes(data)
-    fixed = ICIP2024_HEADER.size + ICIP2024_LENGTHS.size
-    if len(data) < fixed:
-        raise hip.VcError(f"ICIP2024 container: {len(data)} bytes is shorter than the {fixed}-byte header")
-    magic, version, down_ratio, hz, wz, s, scale1, scale2 = ICIP2024_HEADER.unpack_from(data, 0)
-    if magic != ICIP2024_MAGIC:
-        raise hip.VcError(f"ICIP2024 container: magic {magic!r} is not {ICIP2024_MAGIC!r}")
-    if version != ICIP2024_VERSION:
-        raise hip.VcError(f"ICIP2024 container: version {version} (this reader knows {ICIP2024_VERSION})")
-    if down_ratio not in ICIP2024_DOWN_RATIOS or hz < 1 or wz < 1:
-        raise hip.VcError(f"ICIP2024 container: down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} out of range")
-    if not all(np.isfinite(v) for v in (s, scale1, scale2)):
-        raise hip.VcError("ICIP2024 container: a header number is not finite")
-    lengths = ICIP2024_LENGTHS.unpack_from(data, ICIP2024_HEADER.size)
-    if fixed + sum(lengths) != len(data):
-        raise hip.VcError(f"ICIP2024 container: the length table asks for {fixed + sum(lengths)} bytes, the buffer has {len(data)}")
-    parts, pos = [], fixed
-    for n in lengths:
-        parts.append(data[pos:pos + n])
-        pos += n
-    strings = {"offset": [[[p] for p in parts[1:6]], [parts[0]]], "residual": [[[p] for p in parts[7:12]], [parts[6]]]}
-    return {"strings": strings, "shape": (hz, wz), "down_ratio": down_ratio, "s": s, "scale1": scale1, "scale2": scale2}
-
-
-# Container of the device-coded frames (FlowGuidedB.compress(coder="device"); payload format: DESIGN.md section 4d).  Its own
-# magic: a VCIB reader refuses it and this reader refuses VCIB.  Little-endian:
-#   offset  0  the 22 header bytes of VCIB with magic "VCID": version (1), down_ratio, hyper-latent shape, s, scale1, scale2
-#          22  u8       waves W (1, 2, 4, 8 or 16): sub-streams per payload
-#          23  u32 x 2  payload lengths: offset, residual
-#          31  the two payloads in that order
-ICIP2024_DEV_MAGIC = b"VCID"
-ICIP2024_DEV_TAIL = struct.Struct("<BII")
-
-
-def pack_icip2024_frame_dev(strings, shape, down_ratio, s, scale1, scale2, waves, image=0):
-    """The container of image ``image`` of a ``FlowGuidedB.compress(coder="device")`` result (``waves`` as it returns it)."""
-    hz, wz = int(shape[0]), int(shape[1])
-    if int(down_ratio) not in ICIP2024_DOWN_RATIOS or not (1 <= hz <= 0xffff and 1 <= wz <= 0xffff) or not hip.irans_waves_ok(waves):
-        raise hip.VcError(f"down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} / waves {waves} do not fit the container")
-    if not isinstance(strings, dict) or set(strings) != {"offset", "residual"}:
-        raise hip.VcError('strings: {"offset": [payload per image], "residual": [payload per image]}')
-    payloads = [bytes(strings[c][image]) for c in ("offset", "residual")]
-    if any(len(p) > 0xffffffff for p in payloads):
-        raise hip.VcError("a payload is longer than the container's 32-bit length field")
-    head = ICIP2024_HEADER.pack(ICIP2024_DEV_MAGIC, ICIP2024_VERSION, int(down_ratio), hz, wz, float(s), float(scale1), float(scale2))
-    return head + ICIP2024_DEV_TAIL.pack(int(waves), *(len(p) for p in payloads)) + b"".join(payloads)
-
-
-def unpack_icip2024_frame_dev(data):
-    """Inverse of :func:`pack_icip2024_frame_dev`: ``{"strings" (one image per list), "waves", "shape", "down_ratio", "s", "scale1",
-    "scale2"}``; magic, version, field ranges, the wave count, the smallest possible payload and the total length are validated
-    before anything is returned (VcError)."""
-    data = bytes(data)
-    fixed = ICIP2024_HEADER.size + ICIP2024_DEV_TAIL.size
-    if len(data) < fixed:
-        raise hip.VcError(f"ICIP2024 device-coded container: {len(data)} bytes is shorter than the {fixed}-byte header")
-    magic, version, down_ratio, hz, wz, s, scale1, scale2 = ICIP2024_HEADER.unpack_from(data, 0)
-    if magic != ICIP2024_DEV_MAGIC:
-        raise hip.VcError(f"ICIP2024 device-coded container: magic {magic!r} is not {ICIP2024_DEV_MAGIC!r}")
-    if version != ICIP2024_VERSION:
-        raise hip.VcError(f"ICIP2024 device-coded container: version {version} (this reader knows {ICIP2024_VERSION})")
-    if down_ratio not in ICIP2024_DOWN_RATIOS or hz < 1 or wz < 1:
-        raise hip.VcError(f"ICIP2024 device-coded container: down_ratio {down_ratio} / hyper-latent shape {hz}x{wz} out of range")
-    if not all(np.isfinite(v) for v in (s, scale1, scale2)):
-        raise hip.VcError("ICIP2024 device-coded container: a header number is not finite")
-    waves, n_off, n_res = ICIP2024_DEV_TAIL.unpack_from(data, ICIP2024_HEADER.size)
-    if not hip.irans_waves_ok(waves):
-        raise hip.VcError(f"ICIP2024 device-coded container: waves {waves} is not a power of two in 1..16")
-    if fixed + n_off + n_res != len(data) or min(n_off, n_res) < waves * hip.IRANS_SUBSTREAM_HEADER or n_off % 4 or n_res % 4:
-        raise hip.VcError(f"ICIP2024 device-coded container: payload lengths {n_off} + {n_res} do not fit {len(data)} bytes / {waves} waves")
-    strings = {"offset": [data[fixed:fixed + n_off]], "residual": [data[fixed + n_off:]]}
-    return {"strings": strings, "waves": waves, "shape": (hz, wz), "down_ratio": down_ratio, "s": s, "scale1": scale1, "scale2": scale2}
-
-
-# ------------------------------------------------------------------------------------------------
-# ICIP2024 sequence file: device-coded ELIC I-frames (VCII) and B-frames (VCID) in coding order (VCSQ).  Layout: INTEGRATION.md
-# ------------------------------------------------------------------------------------------------
-# I-frame container, little-endian:
-#   offset  0  4 bytes  magic "VCII"
-#           4  u8       version (1)
-#           5  u8       waves W (1, 2, 4, 8 or 16)
-#           6  u16 x 2  hyper-latent shape (h, w) = frame / 64
-#          10  u32      payload length
-#          14  the payload of ELIC.compress(coder="device") for one image
-ICIP2024_INTRA_MAGIC = b"VCII"
-ICIP2024_INTRA_VERSION = 1
-ICIP2024_INTRA_HEADER = struct.Struct("<4sBBHHI")
-
-
-def pack_icip2024_intra_dev(payload, shape, waves):
-    """The container of one image of an ``ELIC.compress(coder="device")`` result: its payload, "shape" and "waves"."""
-    hz, wz = int(shape[0]), int(shape[1])
-    payload = bytes(payload)
-    if not (1 <= hz <= 0xffff and 1 <= wz <= 0xffff) or not hip.irans_waves_ok(waves):
-        raise hip.VcError(f"hyper-latent shape {hz}x{wz} / waves {waves} do not fit the container")
-    if len(payload) > 0xffffffff or len(payload) % 4 or len(payload) < int(waves) * hip.IRANS_SUBSTREAM_HEADER:
-        raise hip.VcError(f"a payload of {len(payload)} bytes is not one of the interleaved coder with {waves} waves")
-    return ICIP2024_INTRA_HEADER.pack(ICIP2024_INTRA_MAGIC, ICIP2024_INTRA_VERSION, int(waves), hz, wz, len(payload)) + payload
-
-
-def unpack_icip2024_intra_dev(data):
-    """Inverse of :func:`pack_icip2024_intra_dev`: ``{"payload", "waves", "shape"}``; magic, version, the wave count, the smallest
-    possible payload and the total length are validated before anything is returned (VcError)."""
-    data = bytes(data)
-    fixed = ICIP2024_INTRA_HEADER.size
-    if len(data) < fixed:
-        raise hip.VcError(f"ICIP2024 I-frame container: {len(data)} bytes is shorter than the {fixed}-byte header")
-    magic, version, waves, hz, wz, length = ICIP2024_INTRA_HEADER.unpack_from(data, 0)
-    if magic != ICIP2024_INTRA_MAGIC:
-        raise hip.VcError(f"ICIP2024 I-frame container: magic {magic!r} is not {ICIP2024_INTRA_MAGIC!r}")
-    if version != ICIP2024_INTRA_VERSION:
-        raise hip.VcError(f"ICIP2024 I-frame container: version {version} (this reader knows {ICIP2024_INTRA_VERSION})")
-    if not hip.irans_waves_ok(waves):
-        raise hip.VcError(f"ICIP2024 I-frame container: waves {waves} is not a power of two in 1..16")
-    if hz < 1 or wz < 1:
-        raise hip.VcError(f"ICIP2024 I-frame container: hyper-latent shape {hz}x{wz} out of range")
-    if fixed + length != len(data) or length % 4 or length < waves * hip.IRANS_SUBSTREAM_HEADER:
-        raise hip.VcError(f"ICIP2024 I-frame container: payload length {length} does not fit {len(data)} bytes / {waves} waves")
-    return {"payload": data[fixed:], "waves": waves, "shape": (hz, wz)}
-
-
-# Sequence file, little-endian:
-#   offset  0  4 bytes  magic "VCSQ"
-#           4  u8       version (1)
-#           5  u8       model family (1 = ICIP2024; every other value is refused)
-#           6  u16 x 2  picture width, height (unpadded)
-#          10  u32      frame count
-#          14  u16      intra_size
-#          16  f32      quality level s
-#          20  u8       intra quality index
-#          21  one record per frame in CODING order:  u8 type (0 = I, 1 = B) | u32 display order | u32 length | VCII / VCID bytes
-SEQUENCE_MAGIC = b"VCSQ"
-SEQUENCE_VERSION = 1
-SEQUENCE_FAMILY_ICIP2024 = 1
-SEQUENCE_HEADER = struct.Struct("<4sBBHHIHfB")
-SEQUENCE_RECORD = struct.Struct("<BII")
-SEQUENCE_TYPES = ("I", "B")
-
-
-def sequence_plan(intra_size, n_frames):
-    """[(display order, "I" | "B")] in coding order, as the encoder's loop walks it (icip2024.get_order_typ_list).  VcError where
-    that function gives no coding order for the pair: every frame exactly once, the first one an I-frame."""
-    from . import icip2024
-    intra_size, n_frames = int(intra_size), int(n_frames)
-    if intra_size < 1 or n_frames < 1:
-        raise hip.VcError(f"intra_size {intra_size} / {n_frames} frames: both at least 1")
-    if n_frames == 1:
-        return [(0, "I")]
-    order, typ = icip2024.get_order_typ_list(intra_size, n_frames)
-    if sorted(order) != list(range(n_frames)) or len(typ) != n_frames or typ[order[0]] != "I":
-        raise hip.VcError(f"get_order_typ_list({intra_size}, {n_frames}) is no coding order of {n_frames} frames: {order}")
-    return [(o, typ[o]) for o in order]
-
-
-def pack_sequence(records, width, height, intra_size, s, intra_quality, family=SEQUENCE_FAMILY_ICIP2024):
-    """``records``: [(type "I" | "B", display order, container bytes)] in coding order -- checked against :func:`sequence_plan`."""
-    records = [(t, int(o), bytes(b)) for t, o, b in records]
-    if family != SEQUENCE_FAMILY_ICIP2024:
-        raise hip.VcError(f"sequence file: model family {family} (only {SEQUENCE_FAMILY_ICIP2024} = ICIP2024 is defined)")
-    if not (1 <= int(width) <= 0xffff and 1 <= int(height) <= 0xffff and 1 <= int(intra_size) <= 0xffff and 0 <= int(intra_quality) <= 0xff) \
-            or not np.isfinite(float(s)) or not 1 <= len(records) <= 0xffffffff:
-        raise hip.VcError("sequence file: a header field is out of range")
-    if [(o, t) for t, o, _ in records] != sequence_plan(intra_size, len(records)):
-        raise hip.VcError("sequence file: the records are not in the coding order of get_order_typ_list")
-    if any(len(b) > 0xffffffff for _, _, b in records):
-        raise hip.VcError("sequence file: a frame is longer than the 32-bit length field")
-    head = SEQUENCE_HEADER.pack(SEQUENCE_MAGIC, SEQUENCE_VERSION, family, int(width), int(height), len(records), int(intra_size), float(s),
-                                int(intra_quality))
-    return head + b"".join(SEQUENCE_RECORD.pack(SEQUENCE_TYPES.index(t), o, len(b)) + b for t, o, b in records)
-
-
-def unpack_sequence(data):
-    """Inverse of :func:`pack_sequence`: ``{"family", "width", "height", "frames", "intra_size", "s", "intra_quality", "records":
-    [(type, display order, container bytes)] in coding order}``.  Magic, version, family, field ranges, the frame count against the
-    buffer's length (before anything is sized by it), every record's length against the data that is left, the record sequence
-    against :func:`sequence_plan` and the absence of trailing bytes are validated before anything is returned (VcError)."""
-    data = bytes(data)
-    fixed = SEQUENCE_HEADER.size
-    if len(data) < fixed:
-        raise hip.VcError(f"sequence file: {len(data)} bytes is shorter than the {fixed}-byte header")
-    magic, version, family, width, height, frames, intra_size, s, intra_quality = SEQUENCE_HEADER.unpack_from(data, 0)
-    if magic != SEQUENCE_MAGIC:
-        raise hip.VcError(f"sequence file: magic {magic!r} is not {SEQUENCE_MAGIC!r}")
-    if version != SEQUENCE_VERSION:
-        raise hip.VcError(f"sequence file: version {version} (this reader knows {SEQUENCE_VERSION})")
-    if family != SEQUENCE_FAMILY_ICIP2024:
-        raise hip.VcError(f"sequence file: model family {family} (only {SEQUENCE_FAMILY_ICIP2024} = ICIP2024 is defined)")
-    if width < 1 or height < 1 or intra_size < 1 or not np.isfinite(s):
-        raise hip.VcError(f"sequence file: picture {width}x{height} / intra_size {intra_size} / level {s} out of range")
-    if frames < 1 or fixed + frames * SEQUENCE_RECORD.size > len(data):
-        raise hip.VcError(f"sequence file: {frames} frames do not fit {len(data)} bytes")
-    plan = sequence_plan(intra_size, frames)
-    records, pos = [], fixed
-    for k, (order, typ) in enumerate(plan):
-        if pos + SEQUENCE_RECORD.size > len(data):
-            raise hip.VcError(f"sequence file: the data ends before record {k} of {frames}")
-        t, o, length = SEQUENCE_RECORD.unpack_from(data, pos)
-        pos += SEQUENCE_RECORD.size
-        if t >= len(SEQUENCE_TYPES) or (o, SEQUENCE_TYPES[t]) != (order, typ):
-            raise hip.VcError(f"sequence file: record {k} is (order {o}, type {t}), the coding order asks for ({order}, {typ})")
-        if length > len(data) - pos:
-            raise hip.VcError(f"sequence file: record {k} asks for {length} bytes, {len(data) - pos} are left")
-        records.append((typ, o, data[pos:pos + length]))
-        pos += length
-    if pos != len(data):
-        raise hip.VcError(f"sequence file: {len(data) - pos} trailing bytes behind the last record")
-    return {"family": family, "width": width, "height": height, "frames": frames, "intra_size": intra_size, "s": s,
-            "intra_quality": intra_quality, "records": records}
+        finish_all(self.levels)

@@ -169,11 +169,11 @@ def cmd_encode_seq(args):
 
 
 def cmd_decode_seq(args):
-    from vcamd import bitstream, sequence
+    from vcamd import containers, sequence
     dev = _device()
     with open(args.bin, "rb") as f:
         data = f.read()
-    head = bitstream.unpack_sequence(data)
+    head = containers.unpack_sequence(data)
     codec = _seq_codec(args, dev)
     with torch.no_grad():
         frames = codec.decode(data)

@@ -432,6 +432,18 @@ def _cli_predictors(model, frames, n):
     return flow_ab, flow_ab, hh, ww
 
 
+def _motion_difference(model, frames, n, dev):
+    """encode_B.py:74-86: what the motion compressor codes -- the flows from the current frame ("c") to both references, pooled, minus
+    the CLI predictors, as 4 channels (cb - ab | ca - ba).  Returns (diff, flow_ba, flow_ab, hh, ww)."""
+    flow_ba, flow_ab, hh, ww = _cli_predictors(model, frames, n)
+    cur = model._flows(frames, [("c", "b"), ("c", "a")])
+    cur_flows, _, _ = Model._pool_pad(cur, 1.0)
+    diff = T.empty(n, flow_ab.h, flow_ab.w, 4, dev)
+    hip.axpby(cur_flows.images(0, n), flow_ab, 1.0, -1.0, out=diff.channels(0, 2))
+    hip.axpby(cur_flows.images(n, 2 * n), flow_ba, 1.0, -1.0, out=diff.channels(2, 4))
+    return diff, flow_ba, flow_ab, hh, ww
+
+
 def encode_B(model, x_after, x_current, x_before, trace=None):
     """(mv_bits, res_bits) like encode_B.py:71-105 -- note the argument order.
     ``trace``: a dict that receives {"mv": {...}, "res": {...}} = the integers handed to the range coder."""
@@ -440,15 +452,8 @@ def encode_B(model, x_after, x_current, x_before, trace=None):
     xb_, xc_, xa_ = (t.contiguous().float() for t in (x_before, x_current, x_after))
     n = xc_.shape[0]
     dev = xc_.device
-    frames = {"b": xb_, "c": xc_, "a": xa_}
-    flow_ba, flow_ab, hh, ww = _cli_predictors(model, frames, n)
-    cur = model._flows(frames, [("c", "b"), ("c", "a")])
-    cur_flows, _, _ = Model._pool_pad(cur, 1.0)
-    flow_cb, flow_ca = cur_flows.images(0, n), cur_flows.images(n, 2 * n)
-    diff = T.empty(n, flow_ab.h, flow_ab.w, 4, dev)
-    hip.axpby(flow_cb, flow_ab, 1.0, -1.0, out=diff.channels(0, 2))
-    hip.axpby(flow_ca, flow_ba, 1.0, -1.0, out=diff.channels(2, 4))
-    mv_hat = model.mv_compressor.forward_t(diff, BitCounter(dev, max_rows=2 * n))
+    diff, flow_ba, flow_ab, hh, ww = _motion_difference(model, {"b": xb_, "c": xc_, "a": xa_}, n, dev)
+    mv_hat =model.mv_compressor.forward_t(diff, BitCounter(dev, max_rows=2 * n))
     t_mv, t_res = ({}, {}) if trace is not None else (None, None)
     strings, shape = model.mv_compressor.compress_t(diff, trace=t_mv)
     mv_bits = {"strings": strings, "shape": torch.Size(shape)}
@@ -502,18 +507,10 @@ def decode_B(x_before, x_after, model, string_flow, string_res, shape_flow, shap
 
 
 def write_container(path_or_none, lmbda, mv_bits, res_bits):
-    """bits_B.bin (encode_B.py:114-126): u32 lambda | u16x2 mv z-shape | u32 len(mv_y) | u32 len(mv_z) |
-    u16x2 res z-shape | u32 len(res_y) | mv_y | mv_z | res_y | res_z (to EOF); little-endian."""
-    out = bytearray()
-    out += np.array(lmbda, dtype=np.uint32).tobytes()
-    out += np.array(tuple(mv_bits["shape"]), dtype=np.uint16).tobytes()
-    out += np.array(len(mv_bits["strings"][0][0]), dtype=np.uint32).tobytes()
-    out += np.array(len(mv_bits["strings"][1][0]), dtype=np.uint32).tobytes()
-    out += np.array(tuple(res_bits["shape"]), dtype=np.uint16).tobytes()
-    out += np.array(len(res_bits["strings"][0][0]), dtype=np.uint32).tobytes()
-    for s in (mv_bits["strings"][0][0], mv_bits["strings"][1][0], res_bits["strings"][0][0], res_bits["strings"][1][0]):
-        out += s
-    blob = bytes(out)
+    """bits_B.bin (encode_B.py:114-126; the layout is with its writer, containers.pack_bits_b) of one frame's strings."""
+    from .containers import pack_bits_b           # (containers imports this module for check_container_shapes)
+    blob = pack_bits_b(lmbda, mv_bits["shape"], res_bits["shape"], mv_bits["strings"][0][0], mv_bits["strings"][1][0],
+                       res_bits["strings"][0][0], res_bits["strings"][1][0])
     if path_or_none is not None:
         with open(path_or_none, "wb") as f:
             f.write(blob)

@@ -1,4 +1,4 @@
-"""The ICIP2024 models as an end-to-end codec: a sequence of frames in, ONE byte string out (the ``VCSQ`` file of vcamd.bitstream;
+"""The ICIP2024 models as an end-to-end codec: a sequence of frames in, ONE byte string out (the ``VCSQ`` file of vcamd.containers;
 layout in INTEGRATION.md), and the frames back from that string and the two models alone.
 
 The loop is the reference's ``val_sequence_level`` as gop.code_sequence_icip2024 walks it -- coding order and frame types from
@@ -9,7 +9,7 @@ device search (``VCID`` records).  The decoder derives order, types, references 
 uploads the payloads once and enqueues launches only, and it reads the decoders' error words after the last frame is enqueued."""
 import torch
 
-from . import bitstream, hip, icip2024
+from . import containers, hip, icip2024
 
 INTRA_QUALITIES = 256
 
@@ -34,7 +34,7 @@ class Icip2024SequenceCodec:
         Returns ``(data, {order: x_hat})``: the file and the reconstruction of every frame (padded NCHW, as the decoder rebuilds
         it).  ``self.report`` then holds, per display order, ``"size_bits"`` (8 x the record's container bytes) and
         ``"estimate_bits"`` (the device's -log2 p of the coded symbols)."""
-        plan = bitstream.sequence_plan(intra_size, n_frames)
+        plan = containers.sequence_plan(intra_size, n_frames)
         level = self.model._coding_level(level)
         hp, wp = self._padded(int(h), int(w))
         records, recon, sizes, estimates = [], {}, {}, {}
@@ -45,21 +45,21 @@ class Icip2024SequenceCodec:
                 raise hip.VcError(f"frame {order}: {tuple(cur.shape)} is not the padded picture (1, 3, {hp}, {wp})")
             if typ == "I":
                 out = self.i_model.compress(cur, coder="device", waves=self.waves)
-                blob = bitstream.pack_icip2024_intra_dev(out["strings"][0], out["shape"], self.waves)
+                blob = containers.pack_icip2024_intra_dev(out["strings"][0], out["shape"], self.waves)
                 estimate = out["bits"]
             else:
                 ref1, ref2, o1, o2 = icip2024.select_references(None, order, buffer, buffer_order)
                 s1, s2 = icip2024.get_scales(order, o1, o2)
                 out = self.model.compress(ref1, ref2, s1, s2, cur, level, down_ratio=None, coder="device", waves=self.waves)
                 c1, c2 = self.model.convert_scales(s1, s2)
-                blob = bitstream.pack_icip2024_frame_dev(out["strings"], out["shape"], out["down_ratio"], level, c1, c2, self.waves)
+                blob = containers.pack_icip2024_frame_dev(out["strings"], out["shape"], out["down_ratio"], level, c1, c2, self.waves)
                 estimate = out["size_estimate"]
             records.append((typ, order, blob))
             recon[order] = out["x_hat"]
             sizes[order], estimates[order] = 8 * len(blob), estimate
             buffer, buffer_order = icip2024.update_buffer(buffer, buffer_order, hip.clamp01_nchw(out["x_hat"]), order)
         self.report = {"size_bits": sizes, "estimate_bits": {o: float(e) for o, e in estimates.items()}}
-        return bitstream.pack_sequence(records, w, h, intra_size, level, self.intra_quality), recon
+        return containers.pack_sequence(records, w, h, intra_size, level, self.intra_quality), recon
 
     def decode(self, data, frames=None):
         """The frames of :meth:`encode`'s file, ``{order: x_hat}`` (padded NCHW), from the bytes alone.  Every container is
@@ -67,14 +67,14 @@ class Icip2024SequenceCodec:
         after the last frame is enqueued, every one of them before the first VcError is raised.  ``frames``: a dict that receives
         the frames as well -- it stays filled when a VcError is raised (the frames in front of a corrupt payload are whole, it and
         the frames that reference it are not)."""
-        seq = bitstream.unpack_sequence(data)
+        seq = containers.unpack_sequence(data)
         if seq["intra_quality"] != self.intra_quality:
             raise hip.VcError(f"sequence file: coded with I-frame quality index {seq['intra_quality']}, this codec holds {self.intra_quality}")
         hp, wp = self._padded(seq["height"], seq["width"])
         shape = (hp // 64, wp // 64)
         parsed = []
         for typ, order, blob in seq["records"]:
-            got = bitstream.unpack_icip2024_intra_dev(blob) if typ == "I" else bitstream.unpack_icip2024_frame_dev(blob)
+            got = containers.unpack_icip2024_intra_dev(blob) if typ == "I" else containers.unpack_icip2024_frame_dev(blob)
             if tuple(got["shape"]) != shape:
                 raise hip.VcError(f"frame {order}: hyper-latent shape {got['shape']} does not belong to a {seq['width']}x{seq['height']} picture")
             if typ == "B" and got["s"] != seq["s"]:
@@ -99,14 +99,7 @@ class Icip2024SequenceCodec:
                                               waves=got["waves"])["x_hat"]
             frames[order] = x_hat
             buffer, buffer_order = icip2024.update_buffer(buffer, buffer_order, hip.clamp01_nchw(x_hat), order)
-        errors = []
-        for dec in decoders:
-            try:
-                dec.finish()
-            except hip.VcError as e:
-                errors.append(e)
-        if errors:
-            raise errors[0]
+        containers.finish_all(decoders)
         return frames
 
 
