@@ -439,6 +439,22 @@ int vc_msssim(vc_stream s, const float *a, const float *b, int n, int channels, 
               double *msssim_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Decoded picture hash (csrc/picture_hash.hip): a 64-bit hash of the 32-bit words of a tensor, defined so that any
+ * summation order gives the same bits --
+ *   mix(t):  t += 0x9E3779B97F4A7C15;  t = (t ^ (t >> 30)) * 0xBF58476D1CE4E5B9;  t = (t ^ (t >> 27)) * 0x94D049BB133111EB;
+ *            return t ^ (t >> 31)                                                   (uint64, wrapping)
+ *   hash(w[0..count)) = mix(count) + sum_i mix(((uint64_t)i << 32) | w[i])          (mod 2^64)
+ * vc_picture_hash: n images of `count` words each, `image_pitch` words apart (the word index i is the index within the
+ * image); writes n hashes to hash_out (device).  partials: n * slots uint64 on the device, slots = vc_bits_slots().  One data
+ * launch and one finishing launch for any n, no atomics, nothing read back, capturable.  VC_EINVAL before any launch for null
+ * pointers, n < 1 (or above the 65535 rows of a launch grid), count < 1, count >= 2^32, image_pitch < count, another `slots`,
+ * or a `words` pointer that is not 4-byte aligned (nothing more is asked of it: each image may sit at its own 16-byte phase).
+ * vc_picture_hash_host: the plain restatement of the formula for one image in host memory; needs no GPU. */
+int vc_picture_hash(vc_stream s, const uint32_t *words, int n, size_t count, size_t image_pitch, uint64_t *partials, int slots,
+                    uint64_t *hash_out);
+uint64_t vc_picture_hash_host(const uint32_t *words, size_t count);
+
+/* ------------------------------------------------------------------------------------------
  * Range coder (host).  Replaces compressai._CXX.pmf_to_quantized_cdf and
  * compressai.ans.RansEncoder.encode_with_indexes / RansDecoder.decode_with_indexes as called from
  * EntropyModel.compress/decompress (reached from LHBDC/model/layers.py:97-98,103,108,112).

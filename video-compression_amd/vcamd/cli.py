@@ -5,6 +5,8 @@
     python -m vcamd.cli test --test_path /datasets/UVG/full_test/ --b_pretrained ../new_compression_1626.pth --lmbda 1626
     python -m vcamd.cli encode_seq --frames DIR --out FILE --level S [--intra_size 16] [--weights B.pth --i_weights I.pth | --seeded N]
     python -m vcamd.cli decode_seq --bin FILE --out DIR [--weights B.pth --i_weights I.pth | --seeded N]
+    python -m vcamd.cli encode_seq_lhbdc --frames DIR --out FILE [--l 1626] [--i_qual 7] [--weights B.pth --i_weights I.pth | --seeded N] [--no_hash]
+    python -m vcamd.cli decode_seq_lhbdc --bin FILE --out DIR [--l 1626] [--i_qual 7] [--weights B.pth --i_weights I.pth | --seeded N] [--no_verify]
 
 ``encode_B`` / ``decode_B`` mirror LHBDC/encode_B.py:21-28,108-126 and LHBDC/decode_B.py:23-28,88-124 (same argument
 names and defaults, same ``bits_B.bin`` container, ``decoded.png`` written beside the bitstream); ``test`` mirrors the
@@ -14,6 +16,10 @@ an MS-SSIM column (pytorch-msssim ``ms_ssim`` defaults on the same uint8 crops, 
 ``encode_seq`` / ``decode_seq`` are the ICIP2024 models as a whole-sequence codec (vcamd.sequence): the PNGs of a folder, in name
 order, into one ``VCSQ`` file (device-coded ELIC I-frames and FlowGuidedB B-frames) and back into ``im00001.png`` ... of the unpadded
 picture, from the file and the two checkpoints alone.
+
+``encode_seq_lhbdc`` / ``decode_seq_lhbdc`` do the same with the LHBDC model between mbt2018_mean I-frames (vcamd.sequence.
+LhbdcSequenceCodec): one ``VCLS`` file that carries a hash of every decoded picture unless ``--no_hash`` is given; the decoder recomputes
+the hashes and fails on the first frame whose reconstruction is not the encoder's unless ``--no_verify`` is given.
 
 Checkpoints: ``--weights`` (default ``pretrained_weights/compression_<l>.pth``, as the reference) is loaded with
 ``torch.load(...)["state_dict"]``.  The reference's checkpoints live on Google Drive; where none is present ``--seeded
@@ -146,19 +152,25 @@ def _seq_codec(args, dev):
     return sequence.Icip2024SequenceCodec(model, intra, waves=args.waves, intra_quality=args.i_qual)
 
 
-def cmd_encode_seq(args):
-    dev = _device()
-    names = sorted(n for n in os.listdir(args.frames) if n.lower().endswith(".png"))
+def _png_folder(folder, dev):
+    """(names in coding = name order, h, w, load_frame(i) -> padded NCHW frame on ``dev``) of a folder of PNG frames"""
+    names = sorted(n for n in os.listdir(folder) if n.lower().endswith(".png"))
     if not names:
-        raise hip.VcError(f"{args.frames}: no PNG frames")
-    first = read_png(os.path.join(args.frames, names[0]))
+        raise hip.VcError(f"{folder}: no PNG frames")
+    first = read_png(os.path.join(folder, names[0]))
     h, w = first.shape[:2]
 
     def load_frame(i):
-        rgb = first if i == 0 else read_png(os.path.join(args.frames, names[i]))
+        rgb = first if i == 0 else read_png(os.path.join(folder, names[i]))
         if rgb.shape[:2] != (h, w):
             raise hip.VcError(f"{names[i]}: {rgb.shape[1]}x{rgb.shape[0]}, the sequence is {w}x{h}")
         return hip.frame_from_uint8(torch.from_numpy(rgb).to(dev))
+    return names, h, w, load_frame
+
+
+def cmd_encode_seq(args):
+    dev = _device()
+    names, h, w, load_frame = _png_folder(args.frames, dev)
     codec = _seq_codec(args, dev)
     with torch.no_grad():
         data, _ = codec.encode(load_frame, len(names), args.level, h, w, intra_size=args.intra_size)
@@ -181,6 +193,42 @@ def cmd_decode_seq(args):
     for order in sorted(frames):
         write_png(os.path.join(args.out, f"im{order + 1:05d}.png"), sequence.crop_uint8(frames[order], head["height"], head["width"]))
     print(f"{args.out}: {len(frames)} frames of {head['width']}x{head['height']} from {len(data)} bytes")
+    return frames
+
+
+def _lhbdc_seq_codec(args, dev, **kw):
+    from vcamd import sequence
+    model, intra = sequence.load_lhbdc_models(args.seeded, args.weights, args.i_weights, args.i_qual, args.l, dev)
+    return sequence.LhbdcSequenceCodec(model, intra, lmbda=args.l, waves=args.waves, intra_quality=args.i_qual, **kw)
+
+
+def cmd_encode_seq_lhbdc(args):
+    dev = _device()
+    names, h, w, load_frame = _png_folder(args.frames, dev)
+    codec = _lhbdc_seq_codec(args, dev, picture_hash=not args.no_hash)
+    with torch.no_grad():
+        data, _ = codec.encode(load_frame, len(names), h, w)
+    with open(args.out, "wb") as f:
+        f.write(data)
+    print(f"{args.out}: {len(names)} frames, {len(data)} bytes ({8.0 * len(data) / (len(names) * h * w):.4f} bpp), "
+          f"{'with' if codec.picture_hash else 'without'} picture hashes")
+    return data
+
+
+def cmd_decode_seq_lhbdc(args):
+    from vcamd import containers, sequence
+    dev = _device()
+    with open(args.bin, "rb") as f:
+        data = f.read()
+    head = containers.unpack_lhbdc_sequence(data)
+    codec = _lhbdc_seq_codec(args, dev)
+    with torch.no_grad():
+        frames = codec.decode(data, verify=not args.no_verify)
+    os.makedirs(args.out, exist_ok=True)
+    for order in sorted(frames):
+        write_png(os.path.join(args.out, f"im{order + 1:05d}.png"), sequence.crop_uint8(frames[order], head["height"], head["width"]))
+    print(f"{args.out}: {len(frames)} frames of {head['width']}x{head['height']} from {len(data)} bytes, picture hashes "
+          f"{'verified' if codec.report['verified'] else 'not verified'}")
     return frames
 
 
@@ -248,6 +296,28 @@ def build_parser():
     ds.add_argument("--out", required=True, help="folder for im00001.png ...")
     seq_ckpt(ds)
     ds.set_defaults(fn=cmd_decode_seq)
+
+    def lhbdc_seq_ckpt(p):
+        p.add_argument("--l", type=int, default=1626, choices=LAMBDAS)
+        p.add_argument("--i_qual", type=int, default=7, choices=range(1, 9), help="mbt2018_mean quality of the I-frames, carried in the file")
+        p.add_argument("--weights", default=None, help="LHBDC checkpoint with a 'state_dict' entry (default pretrained_weights/compression_<l>.pth)")
+        p.add_argument("--i_weights", default=None, help="state dict of the mbt2018_mean I-frame codec")
+        p.add_argument("--seeded", type=int, default=None, help="use the synthetic checkpoints of vcamd.seeding with this seed instead")
+        p.add_argument("--waves", type=int, default=4, help="sub-streams per payload of the device coder")
+
+    el = sub.add_parser("encode_seq_lhbdc", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    el.add_argument("--frames", required=True, help="folder of PNG frames, coded in name order")
+    el.add_argument("--out", required=True, help="the VCLS file to write")
+    el.add_argument("--no_hash", action="store_true", help="store no hash of the decoded pictures")
+    lhbdc_seq_ckpt(el)
+    el.set_defaults(fn=cmd_encode_seq_lhbdc)
+
+    dl = sub.add_parser("decode_seq_lhbdc", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    dl.add_argument("--bin", required=True, help="the VCLS file")
+    dl.add_argument("--out", required=True, help="folder for im00001.png ...")
+    dl.add_argument("--no_verify", action="store_true", help="do not recompute the picture hashes of the file")
+    lhbdc_seq_ckpt(dl)
+    dl.set_defaults(fn=cmd_decode_seq_lhbdc)
     return ap
 
 

@@ -1,5 +1,5 @@
-"""Every byte format of the project, host code only: ``bits_B.bin`` (the reference's), VCLD, VCIB, VCID, VCII and VCSQ (this project's
-own; layout tables in INTEGRATION.md).  Nothing here touches a stream, a device tensor or a thread pool.
+"""Every byte format of the project, host code only: ``bits_B.bin`` (the reference's), VCLD, VCIB, VCID, VCII, VCSQ, VCLI and VCLS (this
+project's own; layout tables in INTEGRATION.md).  Nothing here touches a stream, a device tensor or a thread pool.
 
 The formats share what they have in common and nothing else: :class:`Header` (bytes, short buffer, magic, version -- with the
 format's label in every message), :func:`irans_payloads` (the length rule of the interleaved coder's payloads),
@@ -347,3 +347,142 @@ def unpack_sequence(data):
         raise VcError(f"sequence file: {len(data) - pos} trailing bytes behind the last record")
     return {"family": family, "width": width, "height": height, "frames": frames, "intra_size": intra_size, "s": s,
             "intra_quality": intra_quality, "records": records}
+
+
+# ------------------------------------------------------------------------------------------------
+# LHBDC sequence file: device-coded mbt2018_mean I-frames (VCLI) and B-frames (VCLD) in coding order (VCLS).  Layout: INTEGRATION.md
+# ------------------------------------------------------------------------------------------------
+# I-frame container, little-endian:
+#   offset  0  4 bytes  magic "VCLI"
+#           4  u8       version (1)
+#           5  u8       waves W (1, 2, 4, 8 or 16)
+#           6  u16 x 2  hyper-latent shape (h, w) = frame / 64
+#          10  u32      payload length
+#          14  the payload of ImageMeanScaleHyperprior.compress(coder="device") for one image (two segments, as a VCLD payload)
+LHBDC_INTRA_MAGIC = b"VCLI"
+LHBDC_INTRA_VERSION = 1
+LHBDC_INTRA_HEADER = struct.Struct("<4sBBHHI")
+_VCLI = Header("LHBDC I-frame container", LHBDC_INTRA_MAGIC, LHBDC_INTRA_VERSION, LHBDC_INTRA_HEADER)
+
+
+def pack_lhbdc_intra_dev(payload, shape, waves):
+    """The container of one image of an ``ImageMeanScaleHyperprior.compress(coder="device")`` result: its payload, "shape" and
+    "waves"."""
+    hz, wz = int(shape[0]), int(shape[1])
+    payload = bytes(payload)
+    if not (1 <= hz <= 0xffff and 1 <= wz <= 0xffff):
+        raise VcError(f"hyper-latent shape {hz}x{wz} does not fit the container")
+    _fits_u32("a payload", (payload,))
+    irans_payloads(_VCLI.label, waves, (len(payload),), 0, payload)
+    return _VCLI.pack(int(waves), hz, wz, len(payload)) + payload
+
+
+def unpack_lhbdc_intra_dev(data):
+    """Inverse of :func:`pack_lhbdc_intra_dev`: ``{"payload", "waves", "shape"}``; magic, version, the wave count, the smallest
+    possible payload and the total length are validated before anything is returned (VcError)."""
+    data, (waves, hz, wz, length) = _VCLI.unpack(data)
+    if hz < 1 or wz < 1:
+        raise VcError(f"{_VCLI.label}: hyper-latent shape {hz}x{wz} out of range")
+    (payload,) = irans_payloads(_VCLI.label, waves, (length,), _VCLI.size, data)
+    return {"payload": payload, "waves": waves, "shape": (hz, wz)}
+
+
+# Sequence file, little-endian:
+#   offset  0  4 bytes  magic "VCLS"
+#           4  u8       version (1)
+#           5  u8       flags: bit 0 = every record carries the hash of its decoded picture; every other bit is refused
+#           6  u16 x 2  picture width, height (unpadded)
+#          10  u32      frame count N
+#          14  u32      lambda (as bits_B.bin and VCLD)
+#          18  u8       intra quality (1..8: the mbt2018_mean quality of the I-frames)
+#          19  one record per frame in CODING order:
+#                u8 type (0 = I, 1 = B) | u32 display order | u32 length | u64 picture hash (only with flag bit 0) | VCLI / VCLD bytes
+LHBDC_SEQUENCE_MAGIC = b"VCLS"
+LHBDC_SEQUENCE_VERSION = 1
+LHBDC_SEQUENCE_HASHES = 1                # flag bit 0
+LHBDC_SEQUENCE_HEADER = struct.Struct("<4sBBHHIIB")
+LHBDC_SEQUENCE_RECORD = struct.Struct("<BII")
+LHBDC_SEQUENCE_HASH = struct.Struct("<Q")
+LHBDC_GOP = 8
+_VCLS = Header("LHBDC sequence file", LHBDC_SEQUENCE_MAGIC, LHBDC_SEQUENCE_VERSION, LHBDC_SEQUENCE_HEADER)
+
+
+def lhbdc_sequence_plan(n_frames):
+    """[(display order, "I" | "B")] in coding order for N frames: I(0); for each of the (N - 1) // 8 whole GOPs its closing I-frame
+    8k + 8, then its seven B-frames in hierarchy order (gop.LEVEL_GROUPS: 4; 2, 6; 1, 3, 5, 7); then the (N - 1) % 8 frames behind
+    the last whole GOP as I-frames in display order.  A boundary I-frame is listed (and coded) once."""
+    from .gop import LEVEL_GROUPS
+    n_frames = int(n_frames)
+    if n_frames < 1:
+        raise VcError(f"{n_frames} frames: at least 1")
+    gops = (n_frames - 1) // LHBDC_GOP
+    plan = [(0, "I")]
+    for k in range(gops):
+        plan.append((LHBDC_GOP * k + LHBDC_GOP, "I"))
+        plan.extend((LHBDC_GOP * k + o, "B") for group in LEVEL_GROUPS for o in group)
+    plan.extend((o, "I") for o in range(LHBDC_GOP * gops + 1, n_frames))
+    return plan
+
+
+def _lhbdc_sequence_numbers(width, height, lmbda, intra_quality):
+    width, height, lmbda, intra_quality = int(width), int(height), int(lmbda), int(intra_quality)
+    if not (1 <= width <= 0xffff and 1 <= height <= 0xffff and 0 <= lmbda <= 0xffffffff and 1 <= intra_quality <= 8):
+        raise VcError(f"{_VCLS.label}: picture {width}x{height} / lambda {lmbda} / intra quality {intra_quality} (1..8) out of range")
+    return width, height, lmbda, intra_quality
+
+
+def pack_lhbdc_sequence(records, width, height, lmbda, intra_quality, hashes=None):
+    """``records``: [(type "I" | "B", display order, container bytes)] in coding order -- checked against
+    :func:`lhbdc_sequence_plan`.  ``hashes``: {display order: uint64 hash of the decoded picture} for every frame, or None for a
+    file without hashes (flag bit 0 clear)."""
+    records = [(t, int(o), bytes(b)) for t, o, b in records]
+    width, height, lmbda, intra_quality = _lhbdc_sequence_numbers(width, height, lmbda, intra_quality)
+    if not 1 <= len(records) <= 0xffffffff:
+        raise VcError(f"{_VCLS.label}: {len(records)} frames do not fit the header")
+    if [(o, t) for t, o, _ in records] != lhbdc_sequence_plan(len(records)):
+        raise VcError(f"{_VCLS.label}: the records are not in the coding order of lhbdc_sequence_plan")
+    _fits_u32("a frame", [b for _, _, b in records])
+    if hashes is not None and (sorted(hashes) != list(range(len(records))) or not all(0 <= int(v) <= 0xffffffffffffffff for v in hashes.values())):
+        raise VcError(f"{_VCLS.label}: one 64-bit picture hash per frame")
+    flags = 0 if hashes is None else LHBDC_SEQUENCE_HASHES
+    parts = [_VCLS.pack(flags, width, height, len(records), lmbda, intra_quality)]
+    for t, o, b in records:
+        parts.append(LHBDC_SEQUENCE_RECORD.pack(SEQUENCE_TYPES.index(t), o, len(b)))
+        if hashes is not None:
+            parts.append(LHBDC_SEQUENCE_HASH.pack(int(hashes[o])))
+        parts.append(b)
+    return b"".join(parts)
+
+
+def unpack_lhbdc_sequence(data):
+    """Inverse of :func:`pack_lhbdc_sequence`: ``{"flags", "width", "height", "frames", "lmbda", "intra_quality", "records": [(type,
+    display order, container bytes)] in coding order, "hashes": {display order: int} or None}``.  Magic, version, flags, field
+    ranges, the frame count against the buffer's length (before anything is sized by it), every record's type and order against
+    :func:`lhbdc_sequence_plan`, every length against the data that is left and the absence of trailing bytes are validated
+    before anything is returned (VcError)."""
+    data, (flags, width, height, frames, lmbda, intra_quality) = _VCLS.unpack(data)
+    if flags & ~LHBDC_SEQUENCE_HASHES:
+        raise VcError(f"{_VCLS.label}: flags {flags:#04x} (only bit 0, picture hashes, is defined)")
+    _lhbdc_sequence_numbers(width, height, lmbda, intra_quality)
+    fixed = LHBDC_SEQUENCE_RECORD.size + (LHBDC_SEQUENCE_HASH.size if flags & LHBDC_SEQUENCE_HASHES else 0)
+    if frames < 1 or _VCLS.size + frames * fixed > len(data):
+        raise VcError(f"{_VCLS.label}: {frames} frames do not fit {len(data)} bytes")
+    plan = lhbdc_sequence_plan(frames)
+    records, hashes, pos = [], ({} if flags & LHBDC_SEQUENCE_HASHES else None), _VCLS.size
+    for k, (order, typ) in enumerate(plan):
+        if pos + fixed > len(data):
+            raise VcError(f"{_VCLS.label}: the data ends before record {k} of {frames}")
+        t, o, length = LHBDC_SEQUENCE_RECORD.unpack_from(data, pos)
+        if t >= len(SEQUENCE_TYPES) or (o, SEQUENCE_TYPES[t]) != (order, typ):
+            raise VcError(f"{_VCLS.label}: record {k} is (order {o}, type {t}), the coding order asks for ({order}, {typ})")
+        if hashes is not None:
+            (hashes[o],) = LHBDC_SEQUENCE_HASH.unpack_from(data, pos + LHBDC_SEQUENCE_RECORD.size)
+        pos += fixed
+        if length > len(data) - pos:
+            raise VcError(f"{_VCLS.label}: record {k} asks for {length} bytes, {len(data) - pos} are left")
+        records.append((typ, o, data[pos:pos + length]))
+        pos += length
+    if pos != len(data):
+        raise VcError(f"{_VCLS.label}: {len(data) - pos} trailing bytes behind the last record")
+    return {"flags": flags, "width": width, "height": height, "frames": frames, "lmbda": lmbda, "intra_quality": intra_quality,
+            "records": records, "hashes": hashes}

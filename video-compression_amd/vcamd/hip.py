@@ -221,6 +221,8 @@ def lib():
     sig("vc_psnr_uint8", ci, vp, vp, vp, ci, ci, ci, ci, ci, vp, ci, vp)
     sig("vc_msssim_workspace_bytes", sz, ci, ci, ci, ci)
     sig("vc_msssim", ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, cll, ci, vp, sz, vp, vp)
+    sig("vc_picture_hash", ci, vp, vp, ci, sz, sz, vp, ci, vp)
+    sig("vc_picture_hash_host", ctypes.c_uint64, vp, sz)
     sig("vc_gdn", ci, vp, View, vp, vp, ci, View, View)
     sig("vc_pad", ci, vp, View, View)
     sig("vc_pmf_to_quantized_cdf", ci, vp, ci, ci, vp)
@@ -253,7 +255,7 @@ EXPORTED_SYMBOLS = [
     "vc_spynet_preprocess", "vc_spynet_level_input", "vc_spynet_level_input_sp3", "vc_lhbdc_blend", "vc_flex_blend",
     "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_deform_pair", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar", "vc_deform_pair_hxp",
     "vc_attention_gate", "vc_sse_clamp01", "vc_select_flow", "vc_eb_forward", "vc_eb_dequant", "vc_gc_forward", "vc_gc_indexes", "vc_refine_scales",
-    "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_gc_forward_ckbd", "vc_gc_indexes_ckbd", "vc_gc_dequant_ckbd", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
+    "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_gc_forward_ckbd", "vc_gc_indexes_ckbd", "vc_gc_dequant_ckbd", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_picture_hash", "vc_picture_hash_host", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
     "vc_irans_bound", "vc_irans_wave_words", "vc_irans_encode_host", "vc_irans_decode_host", "vc_irans_pack_tables",
     "vc_irans_tables_in_lds", "vc_irans_encode", "vc_irans_decode_begin", "vc_irans_decode",
@@ -1037,6 +1039,35 @@ def msssim_uint8(x_hat, x, h, w, out=None, quantize=True, terms=False):
                                             workspace.data_ptr(), nbytes, None if t is None else t.data_ptr(), out.data_ptr()),
                             "vc_msssim"))
     return (out, t) if terms else out
+
+
+def picture_hash(x, out=None):
+    """The decoded picture hash (include/vc_hip.h: "Decoded picture hash") of every image of a contiguous fp32 or int32 CUDA tensor
+    [n, ...], its elements taken as 32-bit words: an int64 device tensor [n] holding the uint64 bits (``out``: a contiguous int64
+    view of that shape to write into).  Two launches for any n, no host synchronisation."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in (torch.float32, torch.int32) or x.dim() < 1:
+        raise VcError("picture_hash takes a fp32 or int32 CUDA tensor [n, ...]")
+    if not x.is_contiguous():
+        raise VcError("picture_hash: the tensor must be contiguous (the hash is one of its words in memory order)")
+    n = x.shape[0]
+    count = x.numel() // n if n else 0
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=x.device)
+    elif out.dtype != torch.int64 or out.numel() != n or not out.is_contiguous() or out.device != x.device:
+        raise VcError("picture_hash: out is a contiguous int64 view with one element per image")
+    slots = lib().vc_bits_slots()
+    partials = torch.empty(max(n, 1) * slots, dtype=torch.int64, device=x.device)
+    check(lib().vc_picture_hash(stream(), x.data_ptr(), n, count, count, partials.data_ptr(), slots, out.data_ptr()), "vc_picture_hash")
+    return out
+
+
+def picture_hash_host(array):
+    """The same hash of ONE image held in a numpy array of a 4-byte element type (float32, int32, uint32), through the library's
+    host twin (vc_picture_hash_host): a Python int in 0 .. 2^64 - 1.  Needs no GPU."""
+    a = np.ascontiguousarray(array)
+    if a.dtype.itemsize != 4 or a.dtype.kind not in "fiu" or a.size < 1:
+        raise VcError("picture_hash_host takes a non-empty array of float32, int32 or uint32")
+    return int(lib().vc_picture_hash_host(a.ctypes.data, a.size))
 
 
 def nchw_frames_to_nhwc(frames, out=None):

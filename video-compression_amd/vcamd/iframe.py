@@ -50,16 +50,70 @@ class ImageMeanScaleHyperprior(MeanScaleHyperprior):
         x_hat, tot = self.forward_device(x, likelihoods=lik)
         return {"x_hat": x_hat, "likelihoods": lik, "bits": {"y": tot[:, 0].sum(), "z": tot[:, 1].sum()}}
 
-    def compress(self, x):
+    CODERS = ("host", "device")
+
+    def _check_coder(self, coder, waves):
+        if coder not in self.CODERS or not hip.irans_waves_ok(waves):
+            raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {self.CODERS}, waves a power of two in 1..16")
+
+    def compress(self, x, coder="host", waves=4):
+        """``coder="host"`` (default): CompressAI's ``{"strings": [y strings, z strings], "shape"}`` from the host range coder.
+
+        ``coder="device"``: "strings" is one payload of the interleaved coder per image -- two segments, z with the factorised tables
+        then y with the Gaussian ones, one vc_irans_encode launch on the tensors of code_t, as a payload of a ``VCLD`` container --
+        and the result gains "x_hat" (the clamped reconstruction: bit for bit what ``decompress(coder="device")`` returns), "bits"
+        (0-dim float64 device tensor: -log2 p of the coded symbols), "coder" and "waves"."""
         _require_cuda(x)
+        if coder != "host":
+            self._check_coder(coder, waves)
+            return self._compress_device(x, waves)
         strings, (hz, wz) = self.compress_t(hip.nchw_to_nhwc(x.contiguous().float()))
         return {"strings": strings, "shape": torch.Size([hz, wz])}
 
-    def decompress(self, strings, shape):
+    def decompress(self, strings, shape, coder="host", waves=None):
+        """``coder="device"`` reads the payloads of ``compress(coder="device")`` (``waves`` as it returned it), or a
+        hip.IransDecoder that already uploaded them: launches only; the decoder's error words are read once at the end (VcError)
+        -- by the caller (``finish()`` / containers.finish_all) when it handed in the uploaded decoder."""
+        if coder != "host":
+            if coder not in self.CODERS:
+                raise hip.VcError(f"coder {coder!r}: one of {self.CODERS}")
+            return self._decompress_device(strings, shape, waves)
         assert isinstance(strings, list) and len(strings) == 2
         dev = self.entropy_bottleneck.quantiles.device
         # compressai's MeanScaleHyperprior.decompress clamps the reconstruction to [0, 1]
         return {"x_hat": hip.nhwc_to_nchw(self.decompress_t(strings, shape, dev, final_act=hip.ACT_CLAMP01))}
+
+    # ---- coder="device": the interleaved coder's kernels on both sides, as bitstream.LhbdcStreamCodec(coder="device") ----------
+    def _compress_device(self, x, waves):
+        bits = BitCounter(x.device, max_rows=2)
+        x_hat, sym = self.code_t(hip.nchw_to_nhwc(x.contiguous().float()), bits=bits)
+        n, dev = sym["z_sym"].shape[0], sym["z_sym"].device
+        total = bits.totals().sum()
+        x_hat = hip.nhwc_to_nchw(hip.clamp01(x_hat))           # (exact: equals the decoder's fused ACT_CLAMP01)
+        segments = [(sym["z_sym"], self.z_index_dev(n, sym["shape"], dev), 0), (sym["y_sym"], sym["y_idx"], 1)]
+        tables = [self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()]
+        # the one synchronisation of the pass: the word counts of the payloads, after the last launch
+        payloads = hip.irans_encode(segments, tables, waves)
+        return {"strings": payloads, "shape": torch.Size(sym["shape"]), "x_hat": x_hat, "bits": total, "coder": "device", "waves": int(waves)}
+
+    def _decompress_device(self, strings, shape, waves):
+        hz, wz = int(shape[0]), int(shape[1])
+        if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
+            raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
+        uploaded = isinstance(strings, hip.IransDecoder)
+        if not uploaded:
+            if not (isinstance(strings, (list, tuple)) and strings and all(isinstance(b, (bytes, bytearray)) for b in strings)):
+                raise hip.VcError('decompress(coder="device"): strings is one payload (bytes) per image, as compress(coder="device") '
+                                  "returns it -- this looks like the host-coded [y strings, z strings] lists")
+            self._check_coder("device", waves)
+        dec = strings if uploaded else hip.IransDecoder(strings, waves, self.entropy_bottleneck.quantiles.device)
+        if waves is not None and dec.waves != int(waves):
+            raise hip.VcError(f"the uploaded payloads were read with waves {dec.waves}, not {waves}")
+        scales, means = self.hyper_decode_dev_t(dec, (hz, wz))
+        x_hat = hip.nhwc_to_nchw(self.synth_decode_dev_t(dec, scales, means, final_act=hip.ACT_CLAMP01))
+        if not uploaded:                           # the one read, after everything is enqueued
+            dec.finish()
+        return {"x_hat": x_hat}
 
 
 # compressai.zoo.image.cfgs["mbt2018-mean"]: quality -> (N, M)

@@ -726,10 +726,12 @@ class MeanScaleHyperprior(_Prepared):
                               f"[{y_raw.n},{y_raw.h},{y_raw.w},{y_raw.c}] strides ({y_raw.sn},{y_raw.sh},{y_raw.sw}) is not laid out like y "
                               f"[{y.n},{y.h},{y.w},{y.c}] strides ({y.sn},{y.sh},{y.sw})")
 
-    def _quantise_for_bitstream(self, y, y_raw, z, y_layer, z_layer, gains, want_y_hat, counters=None):
+    def _quantise_for_bitstream(self, y, y_raw, z, y_layer, z_layer, gains, want_y_hat, counters=None, bits=None):
         """Hyper-latent symbols -> z_hat -> (scales, means) -> latent symbols and scale-table indexes, with the boundary cases of both
         roundings decided in fp64 (hip.SYMBOL_REFINE).  Returns (z_sym [n, count], y_sym, y_idx, y_hat or None, (hz, wz)); device
-        int32 tensors.  ``counters``: an int32 device tensor [2] that receives the number of refined (y, z) elements."""
+        int32 tensors.  ``counters``: an int32 device tensor [2] that receives the number of refined (y, z) elements.  ``bits``: a
+        BitCounter that receives two rows for the whole batch, the -log2 p sums of z then y as the two entropy kernels quantise them
+        (a symbol the refinement then moves across its rounding boundary is counted at its first value)."""
         g, ig, hg, hig = gains
         L = hip.lib()
         dev = y.buf.device
@@ -737,7 +739,8 @@ class MeanScaleHyperprior(_Prepared):
         z_sym = torch.empty((z.n, z.c * z.h * z.w), dtype=torch.int32, device=dev)
         eb = self.entropy_bottleneck.device_params()
         hip.check(L.vc_eb_forward(hip.stream(), z.view(), eb.data_ptr(), None if hg is None else hg.data_ptr(),
-                                  None if hig is None else hig.data_ptr(), z_hat.view(), z_sym.data_ptr(), None, 0, None), "vc_eb_forward")
+                                  None if hig is None else hig.data_ptr(), z_hat.view(), z_sym.data_ptr(),
+                                  None if bits is None else bits.next_row_ptr(), 0 if bits is None else bits.slots, None), "vc_eb_forward")
         if z_layer is not None:
             hip.check(L.vc_refine_z_symbols(hip.stream(), z.view(), z_layer, eb.data_ptr(), None if hg is None else hg.data_ptr(),
                                             hip.SYMBOL_REFINE_EPS, z_sym.data_ptr(), z_hat.view(), None if hig is None else hig.data_ptr(),
@@ -751,7 +754,8 @@ class MeanScaleHyperprior(_Prepared):
         table = self._scale_table_dev()
         self._check_sym_src_layout(y, y_raw)
         hip.check(L.vc_gc_forward(hip.stream(), y.view(), scales.view(), means.view(), None, None if ig is None else ig.data_ptr(),
-                                  hip.NULL_VIEW if y_hat is None else y_hat.view(), None, 0, None if y_raw is None else y_raw.ptr,
+                                  hip.NULL_VIEW if y_hat is None else y_hat.view(), None if bits is None else bits.next_row_ptr(),
+                                  0 if bits is None else bits.slots, None if y_raw is None else y_raw.ptr,
                                   y_sym.data_ptr(), y_idx.data_ptr(), table.data_ptr(), table.numel(), None), "vc_gc_forward")
         if y_layer is not None and mu_layer is not None:
             # (Flex-Rate codes the un-gained latent while y_hat comes from the gained one -- quirk B.6: y_hat is then left alone)
@@ -841,13 +845,14 @@ class MeanScaleHyperprior(_Prepared):
         return [y_strings, z_strings], (z.h, z.w)
 
     # -- building blocks of the pipelined bitstream codec (vcamd/bitstream.py) -------------------------------
-    def code_t(self, x, gains=(None, None, None, None), code_ungained_y=False):
+    def code_t(self, x, gains=(None, None, None, None), code_ungained_y=False, bits=None):
         """ONE analysis pass that yields both what an encoder needs: the reconstruction x_hat (exactly what the decoder
         will rebuild from the coded integers) and the integers themselves, left on the device for an asynchronous copy:
         returns (x_hat T, {"y_sym", "y_idx", "z_sym": int32 [n, count], "shape": (hz, wz)}).  Equivalent to
-        forward_t + compress_t without running g_a / h_a / h_s twice."""
+        forward_t + compress_t without running g_a / h_a / h_s twice.  ``bits``: a BitCounter for the estimate of
+        _quantise_for_bitstream (two rows: z, y)."""
         y, y_raw, z, y_layer, z_layer = self._analysis_for_bitstream(x, gains, code_ungained_y)
-        z_sym, y_sym, y_idx, y_hat, _ = self._quantise_for_bitstream(y, y_raw, z, y_layer, z_layer, gains, True)
+        z_sym, y_sym, y_idx, y_hat, _ = self._quantise_for_bitstream(y, y_raw, z, y_layer, z_layer, gains, True, bits=bits)
         x_hat = run_sequential(self.g_s, y_hat, self._cache["g_s"])
         return x_hat, {"y_sym": y_sym, "y_idx": y_idx, "z_sym": z_sym, "shape": (z.h, z.w)}
 
