@@ -316,6 +316,21 @@ int vc_to_half_planar(vc_stream s, vc_view a, int cg, void *out_half);
  * below 4 GiB (32-bit byte offsets).  Everything else -- and every argument vc_deform_pair refuses -- is VC_EINVAL before any launch. */
 int vc_deform_pair_hxp(vc_stream s, vc_view x1, vc_view raw1, vc_view x2, vc_view raw2, const float *wpk, const float *bias,
                        int groups, vc_view out);
+/* Which kernel instance the six entry points above launch -- the rule itself, on the host, launching nothing (what
+ * vc_conv_select_cfg is for the convolutions; tests/test_deform_routing_cpu.py pins the whole table).
+ *   mode    0 vc_deform_conv2d, 1 vc_offset_diversity*, 2 vc_deform_pair*
+ *   x_half  0 fp32 features, 1 half features (_hx), 2 group-planar half features (_hxp)
+ *   vec     the features allow 16-byte gathers: pointers 16-byte aligned (half features: 8-byte), strides % 4 == 0
+ *   rv      1, 2 or 4: the widest pieces, in floats, that pointers and strides of BOTH raw offset tensors allow the records to be
+ *           fetched in (pointer % (4 * rv) == 0, strides % rv == 0); lowered here to what divides the record length 27 * groups / 2;
+ *           ignored for mode 0, which has no records
+ * Returns VC_EINVAL where the entry points refuse before any launch -- a (cg, og) outside the list above, groups odd, < 2 or > 32,
+ * (12, 12) with more than 8 groups per reference, half features that the one fast instance does not serve --, otherwise the
+ * template arguments of k_deform<cg, og, mode, VEC, RV, MAXT, XH> (csrc/deform.hip) as
+ *   VEC | RV << 1 | (MAXT == 512) << 4 | XH << 5
+ * (MAXT: the workgroup-size bound, 512 or 1024 threads; XH: the half-precision gather body).  Two refusals depend on more than these
+ * seven numbers and stay in the launcher: dynamic LDS above the device's limit, half features of 4 GiB or more per image. */
+int vc_deform_select(int mode, int cg, int og, int groups, int x_half, int vec, int rv);
 
 /* Gate of compressai.layers.AttentionBlock (ELIC intra codec of ICIP2024, src/model/elic.py:97-121):
  * out = a * sigmoid(b) + identity. */

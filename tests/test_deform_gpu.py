@@ -1,4 +1,4 @@
-"""-m gpu: every form of csrc/deform.hip's k_deform<CG, OG, FUSED, VEC, RV, MAXT, XH> that the launcher can select, against the
+"""-m gpu: every form of csrc/deform.hip's k_deform<CG, OG, MODE, VEC, RV, MAXT, XH> that the launcher can select, against the
 float64 oracle (tests/deform_ref.py; pinned on the CPU by tests/test_deform_cpu.py).  The forms are reached by shaping the views --
 alignment, strides, group count, record length -- and every case says in a comment which instance it runs.
 
@@ -87,7 +87,7 @@ def _fused(dev, cg, og, groups, h, w, form, raw="dense", with_bias=True):
 @pytest.mark.parametrize("cg,og", dr.PAIRS)
 def test_generic_channel_pairs(dev, cg, og, form, h, w):
     """8 groups, cin / cout = 32/16, 32/32, 64/32, 96/48, 128/64, 64/64, 128/32; with and without mask, with and without bias.
-    vec: k_deform<cg, og, false, true, 1, 512>;  scalar: k_deform<cg, og, false, false, 1, 1024>"""
+    vec: k_deform<cg, og, MODE_GENERIC, true, 1, 512>;  scalar: k_deform<cg, og, MODE_GENERIC, false, 1, 1024>"""
     _generic(dev, cg, og, 8, h, w, form)
 
 
@@ -96,7 +96,7 @@ def test_generic_channel_pairs(dev, cg, og, form, h, w):
 @pytest.mark.parametrize("cg,og", dr.PAIRS)
 def test_fused_channel_pairs(dev, cg, og, form, h, w):
     """8 groups: records of 108 floats, dense raw tensors -> RV = 4.
-    vec: k_deform<cg, og, true, true, 4, 512>;  scalar: k_deform<cg, og, true, false, 4, 1024>"""
+    vec: k_deform<cg, og, MODE_OD, true, 4, 512>;  scalar: k_deform<cg, og, MODE_OD, false, 4, 1024>"""
     _fused(dev, cg, og, 8, h, w, form, with_bias=(h, w) == dr.SIZES[0] or og != 4)       # (bias == nullptr on some of them)
 
 
@@ -106,9 +106,9 @@ def test_fused_channel_pairs(dev, cg, og, form, h, w):
 @pytest.mark.parametrize("raw", ["rv4", "rv2", "rv1"])
 def test_fused_record_width_by_alignment(dev, raw, form, h, w):
     """16 groups of 8 -> 4 channels (the ICIP2024 level-1 shape), records of 216 floats; the raw tensors' alignment decides RV.
-    rv4: vec k_deform<8, 4, true, true, 4, 512>, scalar <8, 4, true, false, 4, 1024>
-    rv2: vec k_deform<8, 4, true, true, 2, 1024>, scalar <8, 4, true, false, 2, 1024>
-    rv1: vec k_deform<8, 4, true, true, 1, 512> (reached by falling out of the FUSED block), scalar <8, 4, true, false, 1, 1024>"""
+    rv4: vec k_deform<8, 4, MODE_OD, true, 4, 512>, scalar <8, 4, MODE_OD, false, 4, 1024>
+    rv2: vec k_deform<8, 4, MODE_OD, true, 2, 1024>, scalar <8, 4, MODE_OD, false, 2, 1024>
+    rv1: vec k_deform<8, 4, MODE_OD, true, 1, 512> (single floats run 512 threads again: there is no <.., true, 2, 512> instance), scalar <8, 4, MODE_OD, false, 1, 1024>"""
     _fused(dev, 8, 4, 16, h, w, form, raw)
 
 
@@ -118,14 +118,14 @@ def test_fused_record_width_by_alignment(dev, raw, form, h, w):
 def test_fused_record_width_by_length(dev, groups, form, h, w):
     """dense, aligned raw tensors whose record length alone limits the pieces: 4 groups (54 floats: RV = 2), 2 groups (27: RV = 1,
     ONE wave per workgroup), 6 groups (81: RV = 1, three waves, odd record arithmetic).
-    G = 4: vec k_deform<8, 4, true, true, 2, 1024>, scalar <8, 4, true, false, 2, 1024>
-    G = 2, 6: vec k_deform<8, 4, true, true, 1, 512>, scalar <8, 4, true, false, 1, 1024>"""
+    G = 4: vec k_deform<8, 4, MODE_OD, true, 2, 1024>, scalar <8, 4, MODE_OD, false, 2, 1024>
+    G = 2, 6: vec k_deform<8, 4, MODE_OD, true, 1, 512>, scalar <8, 4, MODE_OD, false, 1, 1024>"""
     _fused(dev, 8, 4, groups, h, w, form)
 
 
 @pytest.mark.parametrize("groups", [2, 6])
 def test_generic_one_and_three_waves(dev, groups):
-    """half = 1 and 3 on the generic entry: k_deform<8, 4, false, true, 1, 512> / <8, 4, false, false, 1, 1024>"""
+    """half = 1 and 3 on the generic entry: k_deform<8, 4, MODE_GENERIC, true, 1, 512> / <8, 4, MODE_GENERIC, false, 1, 1024>"""
     for form in ("vec", "scalar"):
         _generic(dev, 8, 4, groups, 9, 19, form)
 
@@ -136,7 +136,7 @@ def test_generic_one_and_three_waves(dev, groups):
 @pytest.mark.parametrize("cg,og,groups", [(8, 4, 20), (4, 2, 32)])
 def test_generic_1024_threads(dev, cg, og, groups, form, h, w):
     """20 groups (160 -> 80 channels, 640 threads) and 32 groups (128 -> 64, 1024 threads).
-    vec: k_deform<cg, og, false, true, 1, 1024>;  scalar: k_deform<cg, og, false, false, 1, 1024>"""
+    vec: k_deform<cg, og, MODE_GENERIC, true, 1, 1024>;  scalar: k_deform<cg, og, MODE_GENERIC, false, 1, 1024>"""
     _generic(dev, cg, og, groups, h, w, form)
 
 
@@ -144,10 +144,10 @@ def test_generic_1024_threads(dev, cg, og, groups, form, h, w):
 @pytest.mark.parametrize("form", ["vec", "scalar"])
 @pytest.mark.parametrize("cg,og,groups,raw", [(8, 4, 20, "dense"), (4, 2, 32, "dense"), (4, 2, 32, "rv1")])
 def test_fused_1024_threads(dev, cg, og, groups, raw, form, h, w):
-    """20 groups: records of 270 floats -> RV = 2: vec k_deform<8, 4, true, true, 2, 1024>, scalar <8, 4, true, false, 2, 1024>.
-    32 groups: 432 floats -> RV = 4: vec k_deform<4, 2, true, true, 4, 1024>, scalar <4, 2, true, false, 4, 1024> -- 115 456 bytes of
+    """20 groups: records of 270 floats -> RV = 2: vec k_deform<8, 4, MODE_OD, true, 2, 1024>, scalar <8, 4, MODE_OD, false, 2, 1024>.
+    32 groups: 432 floats -> RV = 4: vec k_deform<4, 2, MODE_OD, true, 4, 1024>, scalar <4, 2, MODE_OD, false, 4, 1024> -- 115 456 bytes of
     dynamic LDS at 1024 threads, above 64 KiB: through hipFuncSetAttribute.  The same with raw tensors 4 bytes off:
-    vec k_deform<4, 2, true, true, 1, 1024>, scalar <4, 2, true, false, 1, 1024>."""
+    vec k_deform<4, 2, MODE_OD, true, 1, 1024>, scalar <4, 2, MODE_OD, false, 1, 1024>."""
     _fused(dev, cg, og, groups, h, w, form, raw)
 
 
@@ -155,15 +155,15 @@ def test_fused_1024_threads(dev, cg, og, groups, raw, form, h, w):
 @pytest.mark.parametrize("h,w", dr.TINY)
 @pytest.mark.parametrize("form", ["vec", "scalar"])
 def test_one_pixel_and_one_row(dev, form, h, w):
-    """1 x 1 and 1 x 17: every sample has y0 = -1 or y1 = H.  generic k_deform<8, 4, false, VEC, 1, 512 | 1024> at 8 groups, fused
-    k_deform<8, 4, true, VEC, 4, 512 | 1024> at 16"""
+    """1 x 1 and 1 x 17: every sample has y0 = -1 or y1 = H.  generic k_deform<8, 4, MODE_GENERIC, VEC, 1, 512 | 1024> at 8 groups, fused
+    k_deform<8, 4, MODE_OD, VEC, 4, 512 | 1024> at 16"""
     _generic(dev, 8, 4, 8, h, w, form)
     _fused(dev, 8, 4, 16, h, w, form)
 
 
 @pytest.mark.parametrize("h,w", dr.SIZES)
 def test_aligned_pointer_with_odd_pixel_stride_is_scalar(dev, h, w):
-    """features at a 16-byte-aligned pointer but sw = c + 1: k_deform<8, 4, false, false, 1, 1024> and <8, 4, true, false, 4, 1024>"""
+    """features at a 16-byte-aligned pointer but sw = c + 1: k_deform<8, 4, MODE_GENERIC, false, 1, 1024> and <8, 4, MODE_OD, false, 4, 1024>"""
     _generic(dev, 8, 4, 8, h, w, "stride")
     _fused(dev, 8, 4, 16, h, w, "stride")
 
@@ -186,7 +186,7 @@ def _planar(x, cg, dev):
 @pytest.mark.parametrize("h,w", dr.SIZES)
 @pytest.mark.parametrize("cg,og", dr.PAIRS)
 def test_half_features_every_pair(dev, cg, og, h, w):
-    """vc_offset_diversity_hx (x_half = 1) and _hxp (x_half = 2), n = 2, 8 groups: k_deform<cg, og, true, true, 4, 512, true>.
+    """vc_offset_diversity_hx (x_half = 1) and _hxp (x_half = 2), n = 2, 8 groups: k_deform<cg, og, MODE_OD, true, 4, 512, true>.
     cg = 4: ONE 8-byte gather per corner (V = 1 with TAIL8); 12: a 16-byte and an 8-byte one; 8, 16: one / two 16-byte ones.
     The Python gate asks cg >= 8, so the entry points are called directly."""
     from vcamd import hip
@@ -218,7 +218,7 @@ def test_half_features_every_pair(dev, cg, og, h, w):
 @pytest.mark.parametrize("c0,cpad", [(0, 8), (4, 8)])
 @pytest.mark.parametrize("cg,og", [(4, 2), (8, 4), (12, 6)])
 def test_half_features_as_a_channel_window(dev, cg, og, c0, cpad):
-    """_hx on features that are channels [c0, c0 + c) of a half buffer 8 channels wider (sw != c): k_deform<cg, og, true, true, 4, 512, true>.
+    """_hx on features that are channels [c0, c0 + c) of a half buffer 8 channels wider (sw != c): k_deform<cg, og, MODE_OD, true, 4, 512, true>.
     c0 = 4: the pointer is 8 bytes off a 16-byte boundary -- the rule of dispatch's aligned8h is 8 bytes (pointer and strides whole
     groups of four halves), which is all the 8- and 16-byte gathers need.  Bit-equal to the dense features' result."""
     from vcamd import hip
@@ -248,8 +248,8 @@ ODD = dict(c0=3, cpad=5, hpad=2, wpad=3, n0=1, npad=2)          # the scalar for
 @pytest.mark.parametrize("win", ["aligned", "odd"])
 def test_generic_on_windows_writes_only_its_window(dev, win, h, w):
     """features, offsets, mask and output are channel slices of wider buffers, crops of larger ones and images [1, 3) of four.
-    aligned: k_deform<8, 4, false, true, 1, 512>, bit-equal to the dense call (the same instance, the same arithmetic);
-    odd: k_deform<8, 4, false, false, 1, 1024>.  Outside its window the output buffer keeps the sentinel bit for bit."""
+    aligned: k_deform<8, 4, MODE_GENERIC, true, 1, 512>, bit-equal to the dense call (the same instance, the same arithmetic);
+    odd: k_deform<8, 4, MODE_GENERIC, false, 1, 1024>.  Outside its window the output buffer keeps the sentinel bit for bit."""
     from vcamd import hip
     kw = ALIGNED if win == "aligned" else ODD
     (x, off, msk, wt, b), refs = _generic_case(8, 4, 8, h, w)
@@ -267,8 +267,8 @@ def test_generic_on_windows_writes_only_its_window(dev, win, h, w):
 @pytest.mark.parametrize("h,w", dr.SIZES)
 @pytest.mark.parametrize("win", ["aligned", "odd"])
 def test_fused_on_windows_writes_only_its_window(dev, win, h, w):
-    """the same for vc_offset_diversity, 16 groups.  aligned: k_deform<8, 4, true, true, 4, 512>, bit-equal to the dense call;
-    odd: k_deform<8, 4, true, false, 1, 1024>"""
+    """the same for vc_offset_diversity, 16 groups.  aligned: k_deform<8, 4, MODE_OD, true, 4, 512>, bit-equal to the dense call;
+    odd: k_deform<8, 4, MODE_OD, false, 1, 1024>"""
     from vcamd import hip
     kw = ALIGNED if win == "aligned" else ODD
     (x1, r1, f1, x2, r2, f2), wt, b, ref = _fused_case(8, 4, 16, h, w)
@@ -289,8 +289,8 @@ def test_fused_on_windows_writes_only_its_window(dev, win, h, w):
 def test_generic_exact_sampling_boundaries(dev, form, h, w):
     """positions exactly at -1, -1 + 2^-10, -0.5, 0, 0.5, S - 1, S - 1 + 2^-10, S - 0.5, S in each axis and in both at the corners
     (exact in float32: the float64 reference takes the kernel's branch at every one), a NaN, a +inf and a -inf offset; pixels whose
-    nine taps all lie outside the image hold the bias exactly (0 without one).  k_deform<8, 4, false, true, 1, 512> /
-    <8, 4, false, false, 1, 1024>"""
+    nine taps all lie outside the image hold the bias exactly (0 without one).  k_deform<8, 4, MODE_GENERIC, true, 1, 512> /
+    <8, 4, MODE_GENERIC, false, 1, 1024>"""
     from vcamd import hip
     x, off, msk, wt, b, slots, dead = dr.boundary_inputs(8, 4, 8, h, w)
     tx, to, tm = dr.place(x, dev, **X_FORMS[form]), dr.place(off, dev), dr.place(msk, dev)

@@ -28,7 +28,7 @@ from vcamd import hip  # noqa: E402
 # entry points that run on the host (weight packing, table construction, the range coder): never stubbed
 HOST = {"vc_version", "vc_abi_version", "vc_target_arch", "vc_conv_select_cfg", "vc_conv_chunk", "vc_conv_packed_weight_floats",
         "vc_conv_packed_bias_floats", "vc_conv_pack_weights", "vc_conv_packed_weight_bytes_f16", "vc_conv_pack_weights_f16",
-        "vc_conv_pack_tail_f16", "vc_conv_packed_weight_bytes_split", "vc_conv_pack_weights_split", "vc_deform_pack_weights",
+        "vc_conv_pack_tail_f16", "vc_conv_packed_weight_bytes_split", "vc_conv_pack_weights_split", "vc_deform_pack_weights", "vc_deform_select",
         "vc_bits_slots", "vc_msssim_workspace_bytes", "vc_pmf_to_quantized_cdf", "vc_rans_bound", "vc_rans_encode_with_indexes",
         "vc_rans_decode_with_indexes", "vc_rans_decode_stream"}
 

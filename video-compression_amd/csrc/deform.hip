@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
         // loads of a thread are all issued before the first one is waited for.  (The first version walked the record
         // with one 4-byte load per thread and iteration, 27 dependent global round trips per workgroup: 54 us of its 60.)
         constexpr int IT = (27 + RV - 1) / RV;
-        const int per_px = 27 * half, pieces = per_px / RV;           // per_px % RV == 0 (checked by the launcher)
+        const int per_px = 27 * half, pieces = per_px / RV;           // per_px % RV == 0 (select_route)
         const int px = threadIdx.x / half, s = threadIdx.x - px * half;
         const int yy = min(ty0 + (px >> twl), H - 1), xx = min(tx0 + (px & twm), W - 1);
         const float *src = O.p + view_off(O, n, yy, xx);
@@ -295,9 +295,7 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
         // measured 7-30 % SLOWER here on the same box (1.47 / 0.63 / 0.19 ms against 1.37 / 0.48 / 0.15 at the three ICIP2024 levels):
         // its shorter instruction stream puts more gathers in flight at once, and this kernel loses L1 hits when it does.
         constexpr int TB = (MAXT > 512 || CG > 8) ? 1 : 3;       // taps per batch (divides 9): 12-24 16-byte gathers in flight per lane
-        constexpr int V = XH ? (CG + 7) / 8 : CG / 4;            // gathers per corner: 16 bytes each; XH with CG % 8 == 4: the last one 8 bytes
-        constexpr int EPV = XH ? 8 : 4;                          // channels per gather
-        constexpr bool TAIL8 = XH && (CG % 8) == 4;
+        constexpr int V = CG / 4;                                // gathers per corner: 16 bytes, four channels each
 #pragma unroll 1
         for (int k0 = 0; k0 < 9; k0 += TB) {     // (rolled: unrolled, the compiler hoists all 9 * CG * OG weight reads and spills)
             Tap q[TB];
@@ -307,17 +305,10 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
                 q[j] = tap(k0 + j);
 #pragma unroll
                 for (int c = 0; c < V; ++c) {
-                    if (TAIL8 && c == V - 1) {
-                        const float2 t1 = *reinterpret_cast<const float2 *>(q[j].p1 + 16 * c), t2 = *reinterpret_cast<const float2 *>(q[j].p2 + 16 * c);
-                        const float2 t3 = *reinterpret_cast<const float2 *>(q[j].p3 + 16 * c), t4 = *reinterpret_cast<const float2 *>(q[j].p4 + 16 * c);
-                        v[j][0][c] = f32x4{t1.x, t1.y, 0.f, 0.f}, v[j][1][c] = f32x4{t2.x, t2.y, 0.f, 0.f};
-                        v[j][2][c] = f32x4{t3.x, t3.y, 0.f, 0.f}, v[j][3][c] = f32x4{t4.x, t4.y, 0.f, 0.f};
-                    } else {
-                        v[j][0][c] = *reinterpret_cast<const f32x4 *>(q[j].p1 + 16 * c);
-                        v[j][1][c] = *reinterpret_cast<const f32x4 *>(q[j].p2 + 16 * c);
-                        v[j][2][c] = *reinterpret_cast<const f32x4 *>(q[j].p3 + 16 * c);
-                        v[j][3][c] = *reinterpret_cast<const f32x4 *>(q[j].p4 + 16 * c);
-                    }
+                    v[j][0][c] = *reinterpret_cast<const f32x4 *>(q[j].p1 + 16 * c);
+                    v[j][1][c] = *reinterpret_cast<const f32x4 *>(q[j].p2 + 16 * c);
+                    v[j][2][c] = *reinterpret_cast<const f32x4 *>(q[j].p3 + 16 * c);
+                    v[j][3][c] = *reinterpret_cast<const f32x4 *>(q[j].p4 + 16 * c);
                 }
             }
 #pragma unroll
@@ -326,22 +317,14 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
 #pragma unroll
                 for (int c = 0; c < V; ++c) {
                     const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-                    const f32x4 v1 = q[j].tl ? v[j][0][c] : z, v2 = q[j].tr ? v[j][1][c] : z;      // (half +0.0 == fp32 +0.0 bit pattern 0)
+                    const f32x4 v1 = q[j].tl ? v[j][0][c] : z, v2 = q[j].tr ? v[j][1][c] : z;
                     const f32x4 v3 = q[j].bl ? v[j][2][c] : z, v4 = q[j].br ? v[j][3][c] : z;
-                    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 #pragma unroll
-                    for (int e = 0; e < ((TAIL8 && c == V - 1) ? 4 : EPV); ++e) {
-                        float e1, e2, e3, e4;
-                        if constexpr (XH) {
-                            e1 = (float)__builtin_bit_cast(h8, v1)[e], e2 = (float)__builtin_bit_cast(h8, v2)[e];
-                            e3 = (float)__builtin_bit_cast(h8, v3)[e], e4 = (float)__builtin_bit_cast(h8, v4)[e];
-                        } else {
-                            e1 = v1[e < 4 ? e : 0], e2 = v2[e < 4 ? e : 0], e3 = v3[e < 4 ? e : 0], e4 = v4[e < 4 ? e : 0];
-                        }
+                    for (int e = 0; e < 4; ++e) {
                         // (a tap outside the image contributes nothing, whatever its modulation value)
-                        const float val = q[j].ok ? (q[j].w1 * e1 + q[j].w2 * e2 + q[j].w3 * e3 + q[j].w4 * e4) * q[j].m : 0.0f;
+                        const float val = q[j].ok ? (q[j].w1 * v1[e] + q[j].w2 * v2[e] + q[j].w3 * v3[e] + q[j].w4 * v4[e]) * q[j].m : 0.0f;
 #pragma unroll
-                        for (int o = 0; o < OG; ++o) acc[o] = fmaf(wk[(EPV * c + e) * OG + o], val, acc[o]);
+                        for (int o = 0; o < OG; ++o) acc[o] = fmaf(wk[(4 * c + e) * OG + o], val, acc[o]);
                     }
                 }
             }
@@ -369,9 +352,74 @@ __global__ void __launch_bounds__(MAXT) k_deform(DeformArgs a)
     for (int o = 0; o < OG; ++o) outp[o] = acc[o];
 }
 
-inline bool aligned16(const vc_view &v)
+// ---- which instance runs --------------------------------------------------------------------------------------------------------
+// The whole rule, from seven integers: what vc_deform_select exports, what the launcher follows and -- through reachable() -- the list
+// of instances this file compiles.  tests/test_deform_routing_cpu.py pins every row of it (tests/golden/deform_routes.json).
+#define VC_DEFORM_SHAPES(X) /* (cg, og): */ X(4, 2) X(4, 4) X(8, 4) /* C = 64 (level 1) */ X(12, 6) /* C = 96 (level 2) */ \
+    X(16, 8) /* C = 128 (level 3) */ X(8, 8) X(16, 4) X(12, 12) /* C = 96 (ICIP2023 level 3) */
+
+constexpr int route(bool vec, int rv, int maxt, bool xh) { return (int)vec | rv << 1 | (maxt == 512) << 4 | (int)xh << 5; }
+
+constexpr int select_route(int mode, int cg, int og, int groups, int x_half, bool vec, int rv)
 {
-    return (reinterpret_cast<uintptr_t>(v.p) % 16 == 0) && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0;
+#define X(CG, OG) (cg == CG && og == OG) ||
+    const bool shape = VC_DEFORM_SHAPES(X) false;
+#undef X
+    if (mode == MODE_GENERIC) rv = 1;                                          // no records
+    if (mode < MODE_GENERIC || mode > MODE_PAIR || x_half < 0 || x_half > 2 || (rv != 1 && rv != 2 && rv != 4)) return VC_EINVAL;
+    if (!shape || groups < 2 || groups % 2 || groups > 32) return VC_EINVAL;   // one wave per group of a reference, 1024 threads at most
+    const int half = groups / 2;
+    while ((27 * half) % rv) rv /= 2;                                          // whole pieces of the 27 * half floats of a record
+    // up to 8 groups per reference (the models' shape) a lane may have 256 registers: MAXT = 512
+    const bool small = half <= 8;
+    // 12 -> 12 channels per group: 144 products per tap and channel next to the gathered values.  The scalar form does not fit the 128
+    // registers of a 1024-thread workgroup (384 bytes per lane spilled), so this pair exists with the 512-thread bound only
+    const bool big = cg * og > 128;
+    if (big && !small) return VC_EINVAL;
+    if (x_half) {
+        // half features: the fast instance (vector gathers, 16-byte record pieces, 512 threads) or nothing, no slower form behind it.
+        // Offset diversity on interleaved or planar ones, every shape but (12, 12); the pair on planar ones at the three shapes of
+        // the ICIP2023 model.
+        const bool served = mode == MODE_OD ? !big : mode == MODE_PAIR && x_half == 2 && cg == og && (cg == 4 || cg == 8 || cg == 12);
+        return served && vec && small && rv == 4 ? route(true, 4, 512, true) : VC_EINVAL;
+    }
+    // MAXT = 512 leaves the vector form the register file for batched gathers (three taps in flight; cg > 8: one); 1024 keeps 128
+    // registers and gathers one tap at a time.  Below (12, 12) the scalar form and 8-byte record pieces (raw tensors 8 bytes off,
+    // records of 54 or 270 floats) have the 1024-thread instances only.
+    const bool t512 = big || (vec && small && rv != 2);
+    return route(vec, rv, t512 ? 512 : 1024, false);
+}
+
+// an instance exists iff the rule can name it (at 8 and 16 groups per reference every record width divides the record)
+constexpr bool reachable(int mode, int cg, int og, int code)
+{
+    for (int groups = 16; groups <= 32; groups += 16)
+        for (int x_half = 0; x_half < 3; ++x_half)
+            for (int vec = 0; vec < 2; ++vec)
+                for (int rv = 1; rv <= 4; rv *= 2)
+                    if (select_route(mode, cg, og, groups, x_half, vec != 0, rv) == code) return true;
+    return false;
+}
+
+typedef void (*deform_kernel)(DeformArgs);
+
+// route code -> k_deform<CG, OG, MODE, VEC, RV, MAXT, XH>, the inverse of route()
+template <int CG, int OG, int MODE, int CODE = 0> deform_kernel instance(int code)
+{
+    if constexpr (CODE < 64) {
+        if constexpr (reachable(MODE, CG, OG, CODE)) {
+            if (code == CODE) return k_deform<CG, OG, MODE, (CODE & 1) != 0, (CODE >> 1) & 7, (CODE & 16) ? 512 : 1024, (CODE & 32) != 0>;
+        }
+        return instance<CG, OG, MODE, CODE + 1>(code);
+    } else {
+        return nullptr;
+    }
+}
+
+// `width` elements of `esz` bytes at a time: the pointer on such a boundary, the strides (in elements) whole multiples
+inline bool pieces_ok(const vc_view &v, int width, int esz = 4)
+{
+    return reinterpret_cast<uintptr_t>(v.p) % (width * esz) == 0 && v.sn % width == 0 && v.sh % width == 0 && v.sw % width == 0;
 }
 
 // Largest LDS allocation of a workgroup on the current device in bytes, queried once per device (0: the query failed).
@@ -392,111 +440,91 @@ inline size_t lds_limit()
     return (size_t)v;
 }
 
-template <int CG, int OG, int MODE> int launch(hipStream_t st, const DeformArgs &a_in, bool vec)
+template <int MODE> int launch(hipStream_t st, DeformArgs a, int cg, int og)
 {
-    constexpr bool FUSED = MODE != MODE_GENERIC;
-    DeformArgs a = a_in;
-    a.gstride = a.x_half == 2 ? (unsigned)((long long)a.x1.h * a.x1.sh * 2) : (unsigned)(CG * (a.x_half ? 2 : 4));
-    const int half = a.groups / 2;
-    if (half > 16) return VC_EINVAL;                       // one wave per group of a half, 1024 threads at most
+    const int half = a.groups / 2, esz = a.x_half ? 2 : 4;
+    // 16-byte gathers of four floats -- or of eight halves that are only 8-byte aligned, which is legal and all that can be asked: a
+    // group's 2 * cg bytes start 8-byte aligned anyway (cg = 4, 12: every other group).  (Every cg served is a multiple of 4.)
+    const bool vec = pieces_ok(a.x1, 4, esz) && pieces_ok(a.x2, 4, esz);
+    // width of the record pieces: what the alignment of the raw offset tensors allows (the rule lowers it to the record length)
+    int rv = 4;
+    while (rv > 1 && !(pieces_ok(a.off1, rv) && pieces_ok(a.off2, rv))) rv /= 2;
+    const int code = select_route(MODE, cg, og, a.groups, a.x_half, vec, rv);
+    if (code < 0) return code;
+    const bool xh = (code & 32) != 0;
+    // half-precision features: 32-bit byte offsets inside one image of the features (24-bit row / pixel multiplies)
+    auto fits32 = [&](const vc_view &v) {
+        return (long long)v.h * v.sh * 2 * (a.x_half == 2 ? half : 1) < (1ll << 32) && v.sh * 2 < (1ll << 24) && v.sw * 2 < (1ll << 24) && v.h < (1 << 24) && v.w < (1 << 24);
+    };
+    if (xh && !(fits32(a.x1) && fits32(a.x2))) return VC_EINVAL;
+    // (the half-precision body reads its weights through the scalar cache: the 64 records alone)
+    const size_t lds = ((xh ? (size_t)0 : (size_t)half * 9 * cg * og) + (MODE != MODE_GENERIC ? 64 * (27 * half + 1) : 0)) * sizeof(float);
+    // more LDS than a workgroup of this device can have (fused, 32 groups of 16 -> 8 channels: 184 KB) is a shape this library does
+    // not serve: refused here, before any launch, like every other unsupported shape
+    if (lds > 64 * 1024 && lds > lds_limit()) return VC_EINVAL;
+    deform_kernel kern = nullptr;
+    switch (cg * 16 + og) {
+#define X(CG, OG) case CG * 16 + OG: kern = instance<CG, OG, MODE>(code); break;
+        VC_DEFORM_SHAPES(X)
+#undef X
+    }
+    if (!kern) return VC_EINVAL;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();                       // (consumed here: the next launch check of the library must not report it as its own)
+        return VC_ELAUNCH;
+    }
+    a.gstride = a.x_half == 2 ? (unsigned)((long long)a.x1.h * a.x1.sh * 2) : (unsigned)(cg * esz);
     // pixels per wave: 4 x 16 on group-planar features, 8 x 8 on pixel-interleaved ones (measured against each other and 2 x 32, 1 x 64)
     a.twl = a.x_half == 2 ? 4 : 3;
     const int tw = 1 << a.twl, th = 64 >> a.twl;
     const unsigned tiles = (unsigned)(((a.out.h + th - 1) / th) * ((a.out.w + tw - 1) / tw));
-    const dim3 grid(tiles, 2u, (unsigned)a.out.n), block((unsigned)(64 * half));
-    // half-precision features: 32-bit byte offsets inside one image of the features (24-bit row / pixel multiplies)
-    auto fits32 = [&](const vc_view &v) {
-        return (long long)v.h * v.sh * 2 * (a.x_half == 2 ? a.groups / 2 : 1) < (1ll << 32) && v.sh * 2 < (1ll << 24) && v.sw * 2 < (1ll << 24) && v.h < (1 << 24) && v.w < (1 << 24);
-    };
-    if (a.x_half && !(fits32(a.x1) && fits32(a.x2))) return VC_EINVAL;
-    const size_t lds = (((vec && a.x_half) ? (size_t)0 : (size_t)half * 9 * CG * OG) + (FUSED ? 64 * (27 * half + 1) : 0)) * sizeof(float);
-    // more LDS than a workgroup of this device can have (fused, 32 groups of 16 -> 8 channels: 184 KB) is a shape this library does
-    // not serve: refused here, before any launch, like every other unsupported shape
-    if (lds > 64 * 1024 && lds > lds_limit()) return VC_EINVAL;
-    auto launch_one = [&](auto kern) {
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();                       // (consumed here: the next launch check of the library must not report it as its own)
-            return VC_ELAUNCH;
-        }
-        hipLaunchKernelGGL(kern, grid, block, lds, st, a);
-        return hipGetLastError() == hipSuccess ? VC_OK : VC_ELAUNCH;
-    };
-    const bool small = half <= 8;
-    if constexpr (CG * OG > 128) {
-        // 12 -> 12 channels per group (ICIP2023 level 3): 144 products per tap and channel next to the gathered values.  The scalar
-        // form does not fit the 128 registers a 1024-thread workgroup leaves a lane (the compiler spilled 384 bytes per lane), so
-        // this pair exists with the 512-thread bound only -- at most 8 groups per reference, which is the model's shape; the vector
-        // form gathers one tap at a time (TB = 1).  fp32 features, with ONE exception: the pair on group-planar half features
-        // (vc_deform_pair_hxp), which keeps no weights in LDS -- the 64 records alone, 54 KiB, no hipFuncSetAttribute.
-        if (!small) return VC_EINVAL;
-        if (a.x_half) {
-            if constexpr (MODE == MODE_PAIR && CG == 12 && OG == 12) {
-                auto ok4 = [&](const vc_view &v) {
-                    return (27 * half) % 4 == 0 && reinterpret_cast<uintptr_t>(v.p) % 16 == 0 && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0;
-                };
-                if (a.x_half == 2 && vec && ok4(a.off1) && ok4(a.off2)) return launch_one(k_deform<12, 12, MODE_PAIR, true, 4, 512, true>);
-            }
-            return VC_EINVAL;
-        }
-        if constexpr (FUSED) {
-            auto ok = [&](const vc_view &v, int w) {
-                return (27 * half) % w == 0 && reinterpret_cast<uintptr_t>(v.p) % (4 * w) == 0 && v.sn % w == 0 && v.sh % w == 0 && v.sw % w == 0;
-            };
-            if (ok(a.off1, 4) && ok(a.off2, 4))
-                return vec ? launch_one(k_deform<CG, OG, MODE, true, 4, 512>) : launch_one(k_deform<CG, OG, MODE, false, 4, 512>);
-            if (ok(a.off1, 2) && ok(a.off2, 2))
-                return vec ? launch_one(k_deform<CG, OG, MODE, true, 2, 512>) : launch_one(k_deform<CG, OG, MODE, false, 2, 512>);
-        }
-        return vec ? launch_one(k_deform<CG, OG, MODE, true, 1, 512>) : launch_one(k_deform<CG, OG, MODE, false, 1, 512>);
-    } else {
-    if constexpr (FUSED) {
-        // width of the record pieces: what the record length and the alignment of the raw offset tensors allow
-        auto ok = [&](const vc_view &v, int w) {
-            return (27 * half) % w == 0 && reinterpret_cast<uintptr_t>(v.p) % (4 * w) == 0 && v.sn % w == 0 && v.sh % w == 0 && v.sw % w == 0;
-        };
-        const int rv = (ok(a.off1, 4) && ok(a.off2, 4)) ? 4 : ((ok(a.off1, 2) && ok(a.off2, 2)) ? 2 : 1);
-        if (a.x_half) {             // half-precision features: the fast fused instance or nothing
-            if constexpr (CG % 4 == 0 && MODE == MODE_OD) {
-                if (vec && small && rv == 4) return launch_one(k_deform<CG, OG, MODE_OD, true, 4, 512, true>);
-            }
-            // the pair: group-planar features only, the two shapes of ICIP2023 below 12 channels per group ((12, 12): above)
-            if constexpr (MODE == MODE_PAIR && CG == OG && (CG == 4 || CG == 8)) {
-                if (a.x_half == 2 && vec && small && rv == 4) return launch_one(k_deform<CG, OG, MODE_PAIR, true, 4, 512, true>);
-            }
-            return VC_EINVAL;
-        }
-        if (vec && small && rv == 4) return launch_one(k_deform<CG, OG, MODE, true, 4, 512>);
-        if (rv == 4) return vec ? launch_one(k_deform<CG, OG, MODE, true, 4>) : launch_one(k_deform<CG, OG, MODE, false, 4>);
-        if (rv == 2) return vec ? launch_one(k_deform<CG, OG, MODE, true, 2>) : launch_one(k_deform<CG, OG, MODE, false, 2>);
-    }
-    if (vec && small) return launch_one(k_deform<CG, OG, MODE, true, 1, 512>);
-    return vec ? launch_one(k_deform<CG, OG, MODE, true>) : launch_one(k_deform<CG, OG, MODE, false>);
-    }
+    hipLaunchKernelGGL(kern, dim3(tiles, 2u, (unsigned)a.out.n), dim3((unsigned)(64 * half)), lds, st, a);
+    return hipGetLastError() == hipSuccess ? VC_OK : VC_ELAUNCH;
 }
 
-template <int MODE> int dispatch(hipStream_t st, const DeformArgs &a, int cg, int og)
+// What the five fused entry points share: the argument contract, checked once, and the kernel's arguments.  MODE_OD with its flow
+// fields, MODE_PAIR without (flow1 / flow2 unused); x_half = 2: x1 / x2 describe ONE group's plane of a dense [n][G/2][h][w][cg] tensor.
+int fused(int mode, int x_half, vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2, vc_view flow2,
+          float magnitude, const float *wpk, const float *bias, int groups, vc_view out)
 {
-    constexpr bool FUSED = MODE != MODE_GENERIC;
-    // (half features: pointer and strides -- in halves -- whole 8-byte units.  That is all the gathers need: a group's 2 * cg bytes
-    //  start 8-byte aligned anyway (cg = 4, 12: every other group), and a 16-byte gather that is only 8-byte aligned is legal)
-    auto aligned8h = [](const vc_view &v) { return (reinterpret_cast<uintptr_t>(v.p) % 8 == 0) && v.sn % 4 == 0 && v.sh % 4 == 0 && v.sw % 4 == 0; };
-    const bool vec = a.x_half ? (cg % 4 == 0 && aligned8h(a.x1) && aligned8h(a.x2)) : (cg % 4 == 0 && aligned16(a.x1) && aligned16(a.x2));
-    if (a.x_half && !FUSED) return VC_EINVAL;
-    switch (cg * 16 + og) {
-    case 4 * 16 + 2: return launch<4, 2, MODE>(st, a, vec);
-    case 4 * 16 + 4: return launch<4, 4, MODE>(st, a, vec);
-    case 8 * 16 + 4: return launch<8, 4, MODE>(st, a, vec);      // C = 64  (level 1)
-    case 12 * 16 + 6: return launch<12, 6, MODE>(st, a, vec);    // C = 96  (level 2)
-    case 16 * 16 + 8: return launch<16, 8, MODE>(st, a, vec);    // C = 128 (level 3)
-    case 8 * 16 + 8: return launch<8, 8, MODE>(st, a, vec);
-    case 16 * 16 + 4: return launch<16, 4, MODE>(st, a, vec);
-    case 12 * 16 + 12: return launch<12, 12, MODE>(st, a, vec);   // C = 96  (ICIP2023 level 3: 8 groups per reference)
+    const bool od = mode == MODE_OD;
+    if (!x1.p || !x2.p || !raw1.p || !raw2.p || !wpk || !out.p || (od && (!flow1.p || !flow2.p))) return VC_EINVAL;
+    if (groups < 2 || groups % 2) return VC_EINVAL;
+    const int half = groups / 2;
+    if (x_half == 2) {
+        for (const vc_view *v : {&x1, &x2})
+            if (v->sw != v->c || v->sh != (long long)v->w * v->c || v->sn != (long long)half * v->h * v->sh) return VC_EINVAL;
+        if (x1.c != x2.c) return VC_EINVAL;
+        x1.c *= half, x2.c *= half;
     }
-    return VC_EINVAL;
+    if (x1.c != x2.c || x1.c % half || out.c % groups || raw1.c != 27 * half || raw2.c != 27 * half) return VC_EINVAL;
+    if (od && (flow1.c < 2 || flow2.c < 2)) return VC_EINVAL;
+    auto sized = [&](const vc_view &v) { return v.h == out.h && v.w == out.w && v.n == out.n; };
+    if (!sized(x1) || !sized(x2) || !sized(raw1) || !sized(raw2) || (od && !(sized(flow1) && sized(flow2)))) return VC_EINVAL;
+    DeformArgs a = {};
+    a.x1 = x1;
+    a.x2 = x2;
+    a.off1 = raw1;
+    a.off2 = raw2;
+    a.flow1 = flow1;
+    a.flow2 = flow2;
+    a.out = out;
+    a.wpk = wpk;
+    a.bias = bias;
+    a.magnitude = magnitude;
+    a.groups = groups;
+    a.x_half = x_half;
+    const int cg = x1.c / half, og = out.c / groups;
+    return od ? launch<MODE_OD>(as_stream(s), a, cg, og) : launch<MODE_PAIR>(as_stream(s), a, cg, og);
 }
 
 }  // namespace
+
+extern "C" int vc_deform_select(int mode, int cg, int og, int groups, int x_half, int vec, int rv)
+{
+    return select_route(mode, cg, og, groups, x_half, vec != 0, rv);
+}
 
 extern "C" int vc_deform_pack_weights(const float *w, int cout, int cg, int groups, float *dst)
 {
@@ -533,27 +561,24 @@ extern "C" int vc_deform_conv2d(vc_stream s, vc_view in, vc_view offset, vc_view
     a.wpk = wpk;
     a.bias = bias;
     a.groups = groups;
-    return dispatch<MODE_GENERIC>(as_stream(s), a, cg, og);
+    return launch<MODE_GENERIC>(as_stream(s), a, cg, og);
 }
-
-static int offset_diversity(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2, vc_view flow2, float magnitude,
-                            const float *wpk, const float *bias, int groups, vc_view out, int x_half);
 
 extern "C" int vc_offset_diversity(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2,
                                    vc_view flow2, float magnitude, const float *wpk, const float *bias, int groups,
                                    vc_view out)
 {
-    return offset_diversity(s, x1, raw1, flow1, x2, raw2, flow2, magnitude, wpk, bias, groups, out, 0);
+    return fused(MODE_OD, 0, s, x1, raw1, flow1, x2, raw2, flow2, magnitude, wpk, bias, groups, out);
 }
 
 // The same with HALF-precision features: x1.p / x2.p point at _Float16 tensors (strides in elements; vc_to_half makes one).
 // fp16 path only -- the gathered values are the features rounded to half, everything else (offsets, modulation, bilinear
-// weights, accumulation) stays fp32; 8 or 16 channels per group, offsets / output as in vc_offset_diversity.
+// weights, accumulation) stays fp32; offsets / output as in vc_offset_diversity.
 extern "C" int vc_offset_diversity_hx(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2,
                                       vc_view flow2, float magnitude, const float *wpk, const float *bias, int groups,
                                       vc_view out)
 {
-    return offset_diversity(s, x1, raw1, flow1, x2, raw2, flow2, magnitude, wpk, bias, groups, out, 1);
+    return fused(MODE_OD, 1, s, x1, raw1, flow1, x2, raw2, flow2, magnitude, wpk, bias, groups, out);
 }
 
 // The same on GROUP-PLANAR half features ([n][G/2][h][w][cg], vc_to_half_planar): x1 / x2 describe ONE group's plane (c = cg, sw = cg,
@@ -563,102 +588,26 @@ extern "C" int vc_offset_diversity_hxp(vc_stream s, vc_view x1, vc_view raw1, vc
                                        vc_view flow2, float magnitude, const float *wpk, const float *bias, int groups,
                                        vc_view out)
 {
-    return offset_diversity(s, x1, raw1, flow1, x2, raw2, flow2, magnitude, wpk, bias, groups, out, 2);
-}
-
-static int offset_diversity(vc_stream s, vc_view x1, vc_view raw1, vc_view flow1, vc_view x2, vc_view raw2, vc_view flow2, float magnitude,
-                            const float *wpk, const float *bias, int groups, vc_view out, int x_half)
-{
-    if (!x1.p || !x2.p || !raw1.p || !raw2.p || !flow1.p || !flow2.p || !wpk || !out.p) return VC_EINVAL;
-    if (groups < 2 || groups % 2) return VC_EINVAL;
-    const int half = groups / 2;
-    if (x_half == 2) {          // planar: the views describe one group's plane
-        if (x1.c != x2.c || x1.sw != x1.c || x2.sw != x2.c || x1.sh != (long long)x1.w * x1.c || x2.sh != (long long)x2.w * x2.c) return VC_EINVAL;
-        if (x1.sn != (long long)half * x1.h * x1.sh || x2.sn != (long long)half * x2.h * x2.sh) return VC_EINVAL;
-        x1.c *= half, x2.c *= half;
-    }
-    if (x1.c != x2.c || x1.c % half || out.c % groups || raw1.c != 27 * half || raw2.c != 27 * half) return VC_EINVAL;
-    if (flow1.c < 2 || flow2.c < 2) return VC_EINVAL;
-    const vc_view *vs[] = {&x1, &x2, &raw1, &raw2, &flow1, &flow2};
-    for (const vc_view *v : vs)
-        if (v->h != out.h || v->w != out.w || v->n != out.n) return VC_EINVAL;
-    DeformArgs a = {};
-    a.x1 = x1;
-    a.x2 = x2;
-    a.off1 = raw1;
-    a.off2 = raw2;
-    a.flow1 = flow1;
-    a.flow2 = flow2;
-    a.out = out;
-    a.wpk = wpk;
-    a.bias = bias;
-    a.magnitude = magnitude;
-    a.groups = groups;
-    a.x_half = x_half;
-    return dispatch<MODE_OD>(as_stream(s), a, x1.c / half, out.c / groups);
+    return fused(MODE_OD, 2, s, x1, raw1, flow1, x2, raw2, flow2, magnitude, wpk, bias, groups, out);
 }
 
 // Two plain modulated DeformConv2d(c, c, 3, padding=1, groups=G/2) layers on two inputs with their outputs concatenated (ICIP2023
 // DeformB.get_deformed_maps, m.py:72-86) as ONE grouped deformable convolution with G groups: groups [0, G/2) read x1 with the first
 // layer's weights, groups [G/2, G) read x2 with the second layer's.  raw_r = that reference's half of the offset head, the record
 // [x-block | y-block | mask-block] of 9 * G/2 channels each: cat(x-block, y-block) IS torchvision's offset tensor, the mask block goes
-// through the logistic; no tanh, no magnitude, no flow.  fp32 features only.
+// through the logistic; no tanh, no magnitude, no flow.  fp32 features.
 extern "C" int vc_deform_pair(vc_stream s, vc_view x1, vc_view raw1, vc_view x2, vc_view raw2, const float *wpk, const float *bias,
                               int groups, vc_view out)
 {
-    if (!x1.p || !x2.p || !raw1.p || !raw2.p || !wpk || !out.p) return VC_EINVAL;
-    if (groups < 2 || groups % 2) return VC_EINVAL;
-    const int half = groups / 2;
-    if (x1.c != x2.c || x1.c % half || out.c % groups || raw1.c != 27 * half || raw2.c != 27 * half) return VC_EINVAL;
-    const vc_view *vs[] = {&x1, &x2, &raw1, &raw2};
-    for (const vc_view *v : vs)
-        if (v->h != out.h || v->w != out.w || v->n != out.n) return VC_EINVAL;
-    DeformArgs a = {};
-    a.x1 = x1;
-    a.x2 = x2;
-    a.off1 = raw1;
-    a.off2 = raw2;
-    a.out = out;
-    a.wpk = wpk;
-    a.bias = bias;
-    a.groups = groups;
-    return dispatch<MODE_PAIR>(as_stream(s), a, x1.c / half, out.c / groups);
+    return fused(MODE_PAIR, 0, s, x1, raw1, vc_view{}, x2, raw2, vc_view{}, 0.0f, wpk, bias, groups, out);
 }
 
-// The same on GROUP-PLANAR half features (fp16 path; the view contract of vc_offset_diversity_hxp: x1 / x2 describe ONE group's plane
-// of a vc_to_half_planar tensor).  One instance per shape of the ICIP2023 model -- k_deform<cg, cg, MODE_PAIR, true, 4, 512, true> for
-// cg = 4, 8, 12 -- and no slower form behind it: whatever that instance does not serve is refused here, before any launch.
+// The same on GROUP-PLANAR half features (fp16 path; the view contract of vc_offset_diversity_hxp).  One instance per shape of the
+// ICIP2023 model -- k_deform<cg, cg, MODE_PAIR, true, 4, 512, true> for cg = 4, 8, 12 -- and no slower form behind it: whatever that
+// instance does not serve is refused by select_route, before any launch.
 extern "C" int vc_deform_pair_hxp(vc_stream s, vc_view x1, vc_view raw1, vc_view x2, vc_view raw2, const float *wpk, const float *bias,
                                   int groups, vc_view out)
 {
-    if (!x1.p || !x2.p || !raw1.p || !raw2.p || !wpk || !out.p) return VC_EINVAL;
-    if (groups < 2 || groups % 2 || groups > 16) return VC_EINVAL;          // at most 8 groups per reference
-    const int half = groups / 2;
-    if (x1.c != x2.c || raw1.c != 27 * half || raw2.c != 27 * half || out.c % groups) return VC_EINVAL;
-    const vc_view *vs[] = {&x1, &x2, &raw1, &raw2};
-    for (const vc_view *v : vs)
-        if (v->h != out.h || v->w != out.w || v->n != out.n) return VC_EINVAL;
-    const int cg = x1.c, og = out.c / groups;
-    if (cg != og || (cg != 4 && cg != 8 && cg != 12)) return VC_EINVAL;
-    for (const vc_view *v : {&x1, &x2}) {
-        // dense planes, [n][G/2][h][w][cg]; 8-byte aligned (a group's pixel is 8, 16 or 24 bytes)
-        if (v->sw != v->c || v->sh != (long long)v->w * v->c || v->sn != (long long)half * v->h * v->sh) return VC_EINVAL;
-        if (reinterpret_cast<uintptr_t>(v->p) % 8) return VC_EINVAL;
-        // 32-bit byte offsets inside one image of the features, 24-bit row / pixel multiplies
-        if ((long long)half * v->h * v->sh * 2 >= (1ll << 32) || v->sh * 2 >= (1ll << 24) || v->h >= (1 << 24) || v->w >= (1 << 24)) return VC_EINVAL;
-    }
-    for (const vc_view *v : {&raw1, &raw2})                                  // records in 16-byte pieces (27 * half floats: half % 4 == 0)
-        if ((27 * half) % 4 || reinterpret_cast<uintptr_t>(v->p) % 16 || v->sn % 4 || v->sh % 4 || v->sw % 4) return VC_EINVAL;
-    x1.c *= half, x2.c *= half;
-    DeformArgs a = {};
-    a.x1 = x1;
-    a.x2 = x2;
-    a.off1 = raw1;
-    a.off2 = raw2;
-    a.out = out;
-    a.wpk = wpk;
-    a.bias = bias;
-    a.groups = groups;
-    a.x_half = 2;
-    return dispatch<MODE_PAIR>(as_stream(s), a, cg, og);
+    return fused(MODE_PAIR, 2, s, x1, raw1, vc_view{}, x2, raw2, vc_view{}, 0.0f, wpk, bias, groups, out);
 }
+

@@ -202,6 +202,7 @@ def lib():
     sig("vc_offset_diversity_hxp", ci, vp, View, View, View, View, View, View, cf, vp, vp, ci, View)
     sig("vc_to_half_planar", ci, vp, View, ci, vp)
     sig("vc_deform_pair_hxp", ci, vp, View, View, View, View, vp, vp, ci, View)
+    sig("vc_deform_select", ci, ci, ci, ci, ci, ci, ci, ci)
     sig("vc_attention_gate", ci, vp, View, View, View, View)
     sig("vc_sse_clamp01", ci, vp, View, View, vp, ci)
     sig("vc_select_flow", ci, vp, vp, ci, ctypes.c_double, ctypes.POINTER(View), View, vp)
@@ -253,7 +254,7 @@ EXPORTED_SYMBOLS = [
     "vc_conv_pack_weights_split", "vc_split3", "vc_split3_pad", "vc_nchw_to_nhwc",
     "vc_nhwc_to_nchw", "vc_u8hwc_to_f32nchw_pad", "vc_f32nchw_to_u8hwc", "vc_avgpool_reflectpad", "vc_maxpool2", "vc_maxpool2_sp3", "vc_avgpool2_sp3", "vc_upsample_bilinear", "vc_upsample_bilinear_sp3", "vc_axpby", "vc_clamp01", "vc_channel_scale", "vc_warp",
     "vc_spynet_preprocess", "vc_spynet_level_input", "vc_spynet_level_input_sp3", "vc_lhbdc_blend", "vc_flex_blend",
-    "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_deform_pair", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar", "vc_deform_pair_hxp",
+    "vc_flex_motion_split", "vc_quantize_mask", "vc_deform_pack_weights", "vc_deform_conv2d", "vc_offset_diversity", "vc_deform_pair", "vc_offset_diversity_hx", "vc_to_half", "vc_offset_diversity_hxp", "vc_to_half_planar", "vc_deform_pair_hxp", "vc_deform_select",
     "vc_attention_gate", "vc_sse_clamp01", "vc_select_flow", "vc_eb_forward", "vc_eb_dequant", "vc_gc_forward", "vc_gc_indexes", "vc_refine_scales",
     "vc_refine_y_symbols", "vc_refine_z_symbols", "vc_gc_dequant", "vc_gc_forward_ckbd", "vc_gc_indexes_ckbd", "vc_gc_dequant_ckbd", "vc_bits_reduce", "vc_bits_slots", "vc_psnr_uint8", "vc_msssim_workspace_bytes", "vc_msssim", "vc_picture_hash", "vc_picture_hash_host", "vc_pmf_to_quantized_cdf", "vc_rans_bound",
     "vc_rans_encode_with_indexes", "vc_rans_decode_with_indexes", "vc_rans_decode_stream",
@@ -1130,6 +1131,26 @@ class PackedDeform:
     def _bias_ptr(self):
         return None if self.bias is None else self.bias.data_ptr()
 
+    def _half_ok(self, x1, raw1, x2, raw2):
+        """fp16 path: may this call gather from half copies of its fp32 features?  The half-feature instances of csrc/deform.hip
+        (vector gathers, <= 8 groups per reference, offset records fetched in 16-byte pieces) and the kernels that make the copies
+        need features AND both raw offset tensors 16-byte aligned, with strides and channel counts in whole float4s."""
+        return (_PRECISION == "fp16" and HALF_DEFORM and self.groups <= 16 and x1.dtype == "f32" and x2.dtype == "f32"
+                and all(t.ptr % 16 == 0 and t.sw % 4 == 0 and t.sh % 4 == 0 and t.sn % 4 == 0 and t.c % 4 == 0 for t in (x1, x2, raw1, raw2)))
+
+    def _planar(self, x):
+        """(group-planar half copy of the features ``x``, the view of ONE group's plane of it that the _hxp entries take)"""
+        cg, hg = self.cin // self.groups, self.groups // 2
+        p = to_half_planar(x, cg)
+        return p, View(p.ptr, x.n, x.h, x.w, cg, hg * x.h * x.w * cg, x.w * cg, cg)
+
+    def _timed(self, key, x, bytes_per_pixel, launch):
+        if timer is None:
+            launch()
+        else:
+            flops = 2.0 * x.n * x.h * x.w * self.cout * (self.cin // self.groups) * 9
+            timer.bracket(f"{key} k3 {self.cin}->{self.cout} g{self.groups} @{x.n}x{x.h}x{x.w}", flops, launch, x.n * x.h * x.w * bytes_per_pixel)
+
     def pair(self, x1, raw1, x2, raw2, out=None):
         """vc_deform_pair: ICIP2023 DeformB.get_deformed_maps in one launch (fp32 features in; on the fp16 path the kernel gathers
         from group-planar half copies made here, vc_deform_pair_hxp)."""
@@ -1138,31 +1159,18 @@ class PackedDeform:
         if out is None:
             out = T.empty(x1.n, x1.h, x1.w, self.cout, x1.buf.device)
         cg, og = self.cin // self.groups, self.cout // self.groups
-        # the half-feature entry has one instance per shape of the model (csrc/deform.hip: (4, 4), (8, 8), (12, 12), <= 8 groups per
-        # reference, records in 16-byte pieces); the alignment conditions are those of offset_diversity below
-        planar = (_PRECISION == "fp16" and HALF_DEFORM and HALF_DEFORM_PLANAR and HALF_DEFORM_PAIR and cg == og and cg in (4, 8, 12)
-                  and self.groups <= 16 and raw1.c % 4 == 0 and raw2.c % 4 == 0
-                  and all(t.ptr % 16 == 0 and t.sw % 4 == 0 and t.sh % 4 == 0 and t.sn % 4 == 0 and t.c % 4 == 0 for t in (x1, x2))
-                  and all(t.ptr % 16 == 0 and t.sw % 4 == 0 and t.sh % 4 == 0 and t.sn % 4 == 0 for t in (raw1, raw2)))
+        # the half-feature entry has one instance per shape of the model: (4, 4), (8, 8), (12, 12)
+        planar = HALF_DEFORM_PLANAR and HALF_DEFORM_PAIR and cg == og and cg in (4, 8, 12) and self._half_ok(x1, raw1, x2, raw2)
+        name = "vc_deform_pair_hxp" if planar else "vc_deform_pair"
         if planar:
-            n_, h_, w_, hg = x1.n, x1.h, x1.w, self.groups // 2
-            p1, p2 = to_half_planar(x1, cg), to_half_planar(x2, cg)
-            v1 = View(p1.ptr, n_, h_, w_, cg, hg * h_ * w_ * cg, w_ * cg, cg)
-            v2 = View(p2.ptr, n_, h_, w_, cg, hg * h_ * w_ * cg, w_ * cg, cg)
+            (_p1, v1), (_p2, v2) = self._planar(x1), self._planar(x2)       # (the copies live until this call returns)
+        else:
+            v1, v2 = x1.view(), x2.view()
 
         def launch():
-            if planar:
-                check(lib().vc_deform_pair_hxp(stream(), v1, raw1.view(), v2, raw2.view(), self.wpk.data_ptr(), self._bias_ptr(),
-                                               self.groups, out.view()), "vc_deform_pair_hxp")
-            else:
-                check(lib().vc_deform_pair(stream(), x1.view(), raw1.view(), x2.view(), raw2.view(), self.wpk.data_ptr(), self._bias_ptr(),
-                                           self.groups, out.view()), "vc_deform_pair")
-        if timer is None:
-            launch()
-        else:
-            flops = 2.0 * x1.n * x1.h * x1.w * self.cout * (self.cin // self.groups) * 9
-            nbytes = x1.n * x1.h * x1.w * ((2.0 if planar else 4.0) * self.cin + 4.0 * (raw1.c + raw2.c + self.cout))
-            timer.bracket(f"deform pair k3 {self.cin}->{self.cout} g{self.groups} @{x1.n}x{x1.h}x{x1.w}", flops, launch, nbytes)
+            check(getattr(lib(), name)(stream(), v1, raw1.view(), v2, raw2.view(), self.wpk.data_ptr(), self._bias_ptr(), self.groups,
+                                       out.view()), name)
+        self._timed("deform pair", x1, (2.0 if planar else 4.0) * self.cin + 4.0 * (raw1.c + raw2.c + self.cout), launch)
         return out
 
     def conv(self, x, offset, mask=None, out=None):
@@ -1176,33 +1184,20 @@ class PackedDeform:
         if out is None:
             out = T.empty(x1.n, x1.h, x1.w, self.cout, x1.buf.device)
         cg = self.cin // self.groups
-        # the half-precision-feature entry has ONE instance (csrc/deform.hip: vector gathers, <= 8 groups per reference, offset
-        # records fetched in 16-byte pieces): features AND both raw offset tensors 16-byte aligned with strides in whole float4s
-        half_x = (_PRECISION == "fp16" and HALF_DEFORM and cg % 4 == 0 and cg >= 8 and self.groups <= 16 and raw1.c % 4 == 0
-                  and raw2.c % 4 == 0 and x1.dtype == "f32" and x2.dtype == "f32"
-                  and all(t.ptr % 16 == 0 and t.sw % 4 == 0 and t.sh % 4 == 0 and t.sn % 4 == 0 and t.c % 4 == 0 for t in (x1, x2))
-                  and all(t.ptr % 16 == 0 and t.sw % 4 == 0 and t.sh % 4 == 0 and t.sn % 4 == 0 for t in (raw1, raw2)))
+        half_x = cg % 4 == 0 and cg >= 8 and self._half_ok(x1, raw1, x2, raw2)
         planar = half_x and HALF_DEFORM_PLANAR
+        name = "vc_offset_diversity_hxp" if planar else ("vc_offset_diversity_hx" if half_x else "vc_offset_diversity")
         if planar:
-            n_, h_, w_ = x1.n, x1.h, x1.w
-            p1, p2 = to_half_planar(x1, cg), to_half_planar(x2, cg)
-            hg = self.groups // 2
-            v1 = View(p1.ptr, n_, h_, w_, cg, hg * h_ * w_ * cg, w_ * cg, cg)
-            v2 = View(p2.ptr, n_, h_, w_, cg, hg * h_ * w_ * cg, w_ * cg, cg)
-        elif half_x:
-            x1, x2 = to_half(x1), to_half(x2)
-        fn = lib().vc_offset_diversity_hxp if planar else (lib().vc_offset_diversity_hx if half_x else lib().vc_offset_diversity)
+            (_p1, v1), (_p2, v2) = self._planar(x1), self._planar(x2)       # (the copies live until this call returns)
+        else:
+            if half_x:
+                x1, x2 = to_half(x1), to_half(x2)
+            v1, v2 = x1.view(True), x2.view(True)
 
         def launch():
-            check(fn(stream(), v1 if planar else x1.view(True), raw1.view(), flow1.view(), v2 if planar else x2.view(True), raw2.view(),
-                     flow2.view(), float(magnitude), self.wpk.data_ptr(), self._bias_ptr(),
-                     self.groups, out.view()), "vc_offset_diversity_hxp" if planar else ("vc_offset_diversity_hx" if half_x else "vc_offset_diversity"))
-        if timer is None:
-            launch()
-        else:
-            flops = 2.0 * x1.n * x1.h * x1.w * self.cout * (self.cin // self.groups) * 9
-            nbytes = x1.n * x1.h * x1.w * ((2.0 if half_x else 4.0) * self.cin + 4.0 * (raw1.c + raw2.c + 4 + self.cout))
-            timer.bracket(f"deform k3 {self.cin}->{self.cout} g{self.groups} @{x1.n}x{x1.h}x{x1.w}", flops, launch, nbytes)
+            check(getattr(lib(), name)(stream(), v1, raw1.view(), flow1.view(), v2, raw2.view(), flow2.view(), float(magnitude),
+                                       self.wpk.data_ptr(), self._bias_ptr(), self.groups, out.view()), name)
+        self._timed("deform", x1, (2.0 if half_x else 4.0) * self.cin + 4.0 * (raw1.c + raw2.c + 4 + self.cout), launch)
         return out
 
 
