@@ -188,6 +188,8 @@ int vc_conv2d_nhwc(vc_stream s, const vc_conv_desc *d);
 
 /* ------------------------------------------------------------------------------------------
  * Layout conversion at the module boundary (reference tensors are NCHW: m.py:32, b_model.py:49)
+ * The NCHW side is dense, the other a view.  VC_EINVAL: a null pointer.  A view with a non-positive n, h, w or c: VC_OK without a
+ * launch.
  * ---------------------------------------------------------------------------------------- */
 int vc_nchw_to_nhwc(vc_stream s, const float *src_nchw, vc_view dst);
 int vc_nhwc_to_nchw(vc_stream s, vc_view src, float *dst_nchw);
@@ -222,7 +224,10 @@ int vc_upsample_bilinear(vc_stream s, vc_view in, vc_view out, int factor, int a
 int vc_upsample_bilinear_sp3(vc_stream s, vc_view in, void *out_split, long long out_image_bytes, int factor, int align_corners, float scale);
 /* out = alpha*a + beta*b (b may be NULL-pointer view with p==0) -- m.py:52,56-59,71 */
 int vc_axpby(vc_stream s, vc_view a, vc_view b, vc_view out, float alpha, float beta);
-/* out = clamp(a, 0, 1) on views: a decoded frame before it serves as a reference (ICIP2024/src/test.py:94, src/utils.py:194) */
+/* out = clamp(a, 0, 1) on views: a decoded frame before it serves as a reference (ICIP2024/src/test.py:94, src/utils.py:194).
+ * Bit for bit torch.clamp: a value inside [0, 1] passes as it is, -0.0 included, and so does a NaN (torch.clamp propagates it; the
+ * earlier fminf(fmaxf()) form gave +0.0 for both).  a may be larger than out (its top-left and first
+ * channels are read) and may alias it. */
 int vc_clamp01(vc_stream s, vc_view a, vc_view out);
 /* out[...,c] = gain[c] * a[...,c] -- Flex Gain_Module.forward (Flex.../b_model/layers.py:54-73) */
 int vc_channel_scale(vc_stream s, vc_view a, const float *gain, vc_view out);
@@ -236,7 +241,8 @@ int vc_channel_scale(vc_stream s, vc_view a, const float *gain, vc_view out);
 enum { VC_WARP_W1 = 1, VC_WARP_W2 = 2, VC_WARP_W3 = 3 };
 int vc_warp(vc_stream s, int convention, vc_view img, vc_view flow, vc_view out);
 
-/* SPyNet pre-processing (flow.py:39-45): NCHW frame -> normalised, channel-flipped NHWC level-0 image */
+/* SPyNet pre-processing (flow.py:39-45): NCHW frame -> normalised, channel-flipped NHWC level-0 image.
+ * VC_EINVAL: a null pointer, dst.c != 3.  A dst with a non-positive n, h or w: VC_OK without a launch. */
 int vc_spynet_preprocess(vc_stream s, const float *src_nchw, vc_view dst);
 /* One pyramid level's network input (flow.py:93-98): up = 2*bilinear_x2(flow_coarse, align_corners=True)
  * (replicate-padded when the level is odd-sized; zeros when flow_coarse.p==NULL), feat = [first,
@@ -248,12 +254,20 @@ int vc_spynet_level_input(vc_stream s, vc_view first, vc_view second, vc_view fl
 int vc_spynet_level_input_sp3(vc_stream s, vc_view first, vc_view second, vc_view flow_coarse, void *feat_split, vc_view up);
 
 /* LHBDC mask blend + residual (m.py:63-67): pred = m*fw + (1-m)*bw ; resid = cur - pred.
- * fwbw holds fw in channels 0..2 and bw in 3..5; mask has 1 channel. resid.p may be NULL. */
+ * fwbw holds fw in channels 0..2 and bw in 3..5; mask has 1 channel. resid.p may be NULL.
+ * pred (3 channels) drives the launch.  VC_EINVAL before any launch: a null fwbw / mask / pred, fwbw.c < 6, pred.c != 3, resid
+ * without cur, and any view (fwbw, mask; cur and resid where their pointer is given) whose n differs from pred's, whose h or w is
+ * smaller than pred's, or with cur.c < 3 or resid.c < 3.  A larger input is read at its top-left.  An empty pred: VC_OK, nothing written. */
 int vc_lhbdc_blend(vc_stream s, vc_view fwbw, vc_view mask, vc_view cur, vc_view pred, vc_view resid);
 /* Flex blend (b_model.py:68-73): mask has 2 channels (already through sigmoid),
- * pred = (.5m0*xb + .5m1*xa)/(.5m0+.5m1+1e-8) ; resid = cur - pred. */
+ * pred = (.5m0*xb + .5m1*xa)/(.5m0+.5m1+1e-8) ; resid = cur - pred.
+ * pred (3 channels) drives the launch.  VC_EINVAL before any launch: a null xb / xa / mask / pred, mask.c < 2, pred.c != 3, xb.c or
+ * xa.c < 3, resid without cur, and any view (xb, xa, mask; cur and resid where their pointer is given) whose n differs from pred's, whose h
+ * or w is smaller than pred's, or with cur.c < 3 or resid.c < 3.  A larger input is read at its top-left.  An empty pred: VC_OK. */
 int vc_flex_blend(vc_stream s, vc_view xb, vc_view xa, vc_view mask, vc_view cur, vc_view pred, vc_view resid);
-/* Flex linear-motion split (b_model.py:38-40): flow4=[F01,F10] -> ft0, ft1 (2 ch each) */
+/* Flex linear-motion split (b_model.py:38-40): flow4=[F01,F10] -> ft0, ft1 (2 ch each).
+ * flow4 drives the launch.  VC_EINVAL before any launch: a null pointer, flow4.c < 4, ft0.c or ft1.c < 2, and an ft0 / ft1 whose n
+ * differs from flow4's or whose h or w is smaller than flow4's (a larger one is written at its top-left).  An empty flow4: VC_OK. */
 int vc_flex_motion_split(vc_stream s, vc_view flow4, vc_view ft0, vc_view ft1, float t);
 
 /* ------------------------------------------------------------------------------------------

@@ -84,6 +84,7 @@ extern "C" int vc_f32nchw_to_u8hwc(vc_stream s, const float *src_nchw, int hp, i
 extern "C" int vc_nchw_to_nhwc(vc_stream s, const float *src, vc_view dst)
 {
     if (!src || !dst.p) return VC_EINVAL;
+    if (dst.n < 1 || dst.h < 1 || dst.w < 1 || dst.c < 1) return VC_OK;
     const long long total = (long long)dst.n * dst.h * dst.w * dst.c;
     hipLaunchKernelGGL(k_nchw_to_nhwc, dim3(ew_grid(total, EW_BLOCK)), dim3(EW_BLOCK), 0, as_stream(s), src, dst);
     VC_LAUNCH_CHECK();
@@ -93,6 +94,7 @@ extern "C" int vc_nchw_to_nhwc(vc_stream s, const float *src, vc_view dst)
 extern "C" int vc_nhwc_to_nchw(vc_stream s, vc_view src, float *dst)
 {
     if (!src.p || !dst) return VC_EINVAL;
+    if (src.n < 1 || src.h < 1 || src.w < 1 || src.c < 1) return VC_OK;
     const long long total = (long long)src.n * src.h * src.w * src.c;
     hipLaunchKernelGGL(k_nhwc_to_nchw, dim3(ew_grid(total, EW_BLOCK)), dim3(EW_BLOCK), 0, as_stream(s), src, dst);
     VC_LAUNCH_CHECK();
@@ -461,7 +463,10 @@ extern "C" int vc_axpby(vc_stream s, vc_view a, vc_view b, vc_view out, float al
 template <bool ROWS> __global__ void k_clamp01(vc_view a, vc_view out, vc_rowmap m)
 {
     ew_for_each<ROWS>(m, out.n, out.h, out.w, out.c, [&](int n, int y, int x, int c) {
-        out.p[view_off(out, n, y, x) + c] = fminf(fmaxf(a.p[view_off(a, n, y, x) + c], 0.0f), 1.0f);
+        // two comparisons, as torch.clamp: a value neither below 0 nor above 1 passes with its bits (fmaxf orders -0.0 below +0.0 and
+        // turned -0.0 into +0.0)
+        const float v = a.p[view_off(a, n, y, x) + c];
+        out.p[view_off(out, n, y, x) + c] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);
     });
 }
 
@@ -828,6 +833,7 @@ __global__ void k_spynet_preprocess(const float *__restrict__ src, vc_view d)
 extern "C" int vc_spynet_preprocess(vc_stream s, const float *src, vc_view dst)
 {
     if (!src || !dst.p || dst.c != 3) return VC_EINVAL;
+    if (dst.n < 1 || dst.h < 1 || dst.w < 1) return VC_OK;
     const long long total = (long long)dst.n * dst.h * dst.w;
     hipLaunchKernelGGL(k_spynet_preprocess, dim3(ew_grid(total, EW_BLOCK)), dim3(EW_BLOCK), 0, as_stream(s), src, dst);
     VC_LAUNCH_CHECK();
@@ -1232,6 +1238,13 @@ extern "C" int vc_split3_pad(vc_stream s, vc_view a, void *out_split, long long 
 // ------------------------------------------------------------------------------------------------
 // blending
 // ------------------------------------------------------------------------------------------------
+// a view the kernel indexes with the pixels of `lead` holds at least `c` channels of them: same image count, no smaller (a larger one
+// is read at its top-left, as vc_axpby does it)
+static inline bool covers(const vc_view &v, const vc_view &lead, int c)
+{
+    return v.n == lead.n && v.h >= lead.h && v.w >= lead.w && v.c >= c;
+}
+
 template <bool ROWS> __global__ void k_lhbdc_blend(vc_view fwbw, vc_view mask, vc_view cur, vc_view pred, vc_view resid, vc_rowmap m)
 {
     ew_for_each<ROWS>(m, pred.n, pred.h, pred.w, 3, [&](int n, int y, int x, int c) {
@@ -1247,7 +1260,9 @@ extern "C" int vc_lhbdc_blend(vc_stream s, vc_view fwbw, vc_view mask, vc_view c
 {
     if (!fwbw.p || !mask.p || !pred.p || fwbw.c < 6 || pred.c != 3) return VC_EINVAL;
     if (resid.p && !cur.p) return VC_EINVAL;
-    if ((long long)pred.n * pred.h * pred.w <= 0) return VC_OK;
+    if (!covers(fwbw, pred, 6) || !covers(mask, pred, 1)) return VC_EINVAL;
+    if ((cur.p && !covers(cur, pred, 3)) || (resid.p && !covers(resid, pred, 3))) return VC_EINVAL;   // (every view that is given)
+    if (pred.n < 1 || pred.h < 1 || pred.w < 1) return VC_OK;
     VC_EW_LAUNCH(as_stream(s), k_lhbdc_blend, pred.n, pred.h, pred.w, 3, fwbw, mask, cur, pred, resid);
     VC_LAUNCH_CHECK();
     return VC_OK;
@@ -1268,7 +1283,9 @@ extern "C" int vc_flex_blend(vc_stream s, vc_view xb, vc_view xa, vc_view mask, 
 {
     if (!xb.p || !xa.p || !mask.p || !pred.p || mask.c < 2 || pred.c != 3) return VC_EINVAL;
     if (resid.p && !cur.p) return VC_EINVAL;
-    if ((long long)pred.n * pred.h * pred.w <= 0) return VC_OK;
+    if (!covers(xb, pred, 3) || !covers(xa, pred, 3) || !covers(mask, pred, 2)) return VC_EINVAL;
+    if ((cur.p && !covers(cur, pred, 3)) || (resid.p && !covers(resid, pred, 3))) return VC_EINVAL;   // (every view that is given)
+    if (pred.n < 1 || pred.h < 1 || pred.w < 1) return VC_OK;
     VC_EW_LAUNCH(as_stream(s), k_flex_blend, pred.n, pred.h, pred.w, 3, xb, xa, mask, cur, pred, resid);
     VC_LAUNCH_CHECK();
     return VC_OK;
@@ -1294,6 +1311,8 @@ __global__ void k_flex_motion_split(vc_view f4, vc_view ft0, vc_view ft1, float 
 extern "C" int vc_flex_motion_split(vc_stream s, vc_view f4, vc_view ft0, vc_view ft1, float t)
 {
     if (!f4.p || !ft0.p || !ft1.p || f4.c < 4) return VC_EINVAL;
+    if (!covers(ft0, f4, 2) || !covers(ft1, f4, 2)) return VC_EINVAL;
+    if (f4.n < 1 || f4.h < 1 || f4.w < 1) return VC_OK;
     const long long total = (long long)f4.n * f4.h * f4.w;
     hipLaunchKernelGGL(k_flex_motion_split, dim3(ew_grid(total, EW_BLOCK)), dim3(EW_BLOCK), 0, as_stream(s), f4, ft0, ft1, t);
     VC_LAUNCH_CHECK();
