@@ -1,6 +1,6 @@
 """-m gpu: the checkerboard entropy kernels of csrc/entropy.hip (vc_gc_forward_ckbd / vc_gc_indexes_ckbd / vc_gc_dequant_ckbd)
 against a numpy restatement: the full-tensor formulae of k_gc_forward / k_gc_indexes / k_gc_dequant in float32, then the slicing
-of ELIC._squeeze_np.
+into the squeezed order include/vc_hip.h documents for these kernels ([n][c][h][w/2]).
 
 Inputs are channel windows of wider tensors, as the model passes them: y = channels [8, 8 + c) of a buffer 16 channels wider,
 (scales, means) = the two halves of one 2c-channel buffer, y_hat = a window of a buffer pre-filled with a sentinel.  The latents
@@ -44,7 +44,7 @@ def table():
 
 
 def squeeze(t, parity):
-    """ELIC._squeeze_np: parity 1 = anchors ((row + col) odd)"""
+    """the squeezed order of the *_ckbd kernels (include/vc_hip.h): parity 1 = anchors ((row + col) odd)"""
     out = np.empty(t.shape[:3] + (t.shape[3] // 2,), dtype=t.dtype)
     out[:, :, 0::2, :] = t[:, :, 0::2, parity::2]
     out[:, :, 1::2, :] = t[:, :, 1::2, (1 - parity)::2]

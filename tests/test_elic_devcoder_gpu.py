@@ -131,6 +131,27 @@ def test_reconstruction_equals_the_host_paths(prod, coded, name):
         assert torch.equal(out["x_hat"][j:j + 1], host_dec[j]["x_hat"]), j
 
 
+def test_host_coded_batch_is_one_string_per_group_for_the_whole_call(prod, coded):
+    """the host-coded format of a batch: one z string per image, ONE string per group for the call -- the anchor integers of all
+    images in [n][c][h][w/2] order, then the non-anchor integers likewise; decoding it rebuilds the single-image decodes"""
+    x, _, trace, host, host_dec = coded("batch2")
+    with torch.no_grad():
+        both = prod.compress(x)
+        dec = prod.decompress(both["strings"], both["shape"])
+    groups, z = both["strings"]
+    assert list(z) == [h["strings"][1][0] for h in host] and isinstance(both["shape"], torch.Size)
+    tables = prod.gaussian_conditional.tables()
+    passes = [(sym.cpu().numpy(), idx.cpu().numpy()) for sym, idx in trace["coded"][1:]]
+    assert len(groups) == 5
+    for g in range(5):
+        (sa, ia), (sn, in_) = passes[2 * g], passes[2 * g + 1]
+        want = hip.rans_encode(np.concatenate([sa.reshape(-1), sn.reshape(-1)]), np.concatenate([ia.reshape(-1), in_.reshape(-1)]), *tables)
+        assert list(groups[g]) == [want], g
+    for g in range(5):
+        assert torch.equal(dec["y_hat"][g], torch.cat([d["y_hat"][g] for d in host_dec])), g
+    assert torch.equal(dec["x_hat"], torch.cat([d["x_hat"] for d in host_dec]))
+
+
 def test_encode_and_decode_do_not_synchronise_early(dev, prod, coded):
     """torch raises on any synchronising call in this mode: the encoder runs up to the collection of the payloads (the launch of
     the coder included) and the decoder from after the upload to x_hat without one (a first pass of the shape has run before:

@@ -101,7 +101,7 @@ def coded(dev, prod):
 
 
 def squeeze(t, parity):
-    """ELIC._squeeze_np: parity 1 = anchors ((row + col) odd)"""
+    """the squeezed order of the *_ckbd kernels (include/vc_hip.h): parity 1 = anchors ((row + col) odd)"""
     out = np.empty(t.shape[:3] + (t.shape[3] // 2,), dtype=t.dtype)
     out[:, :, 0::2, :] = t[:, :, 0::2, parity::2]
     out[:, :, 1::2, :] = t[:, :, 1::2, (1 - parity)::2]
@@ -135,8 +135,8 @@ def test_decoder_rebuilds_the_encoder(dev, prod, coded, name):
 
 @pytest.mark.parametrize("name", ["lhbdc", "batch2"])
 def test_strings_hold_the_symbols_of_the_full_tensor_kernel(dev, prod, coded, name):
-    """vc_gc_forward on the encoder's own (y, scales, means) of every pass: its symbols and indexes, squeezed on the host like
-    ELIC._squeeze_np, are what the group strings decode to -- both parities, every image."""
+    """vc_gc_forward on the encoder's own (y, scales, means) of every pass: its symbols and indexes, squeezed on the host into the
+    order the *_ckbd kernels document, are what the group strings decode to -- both parities, every image."""
     from vcamd import hip
     L = hip.lib()
     _, out, te = coded(name)

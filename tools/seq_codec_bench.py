@@ -4,7 +4,8 @@
   (a) ELIC I-frame compress / decompress: coder="host" (the numpy / one-host-thread path, the yardstick) against coder="device";
   (b) one FlowGuidedB.decompress(coder="device") on the three-launch chain vc_gc_indexes_ckbd -> vc_irans_decode -> vc_gc_dequant_ckbd
       per pass (the product's code; the yardstick) against the fused checkerboard decode (vc_irans_decode_gc_ckbd, one launch per
-      pass: ``_fused_uploaded`` below, the private switch of this tool).  The payloads are uploaded outside the timed span.
+      pass: ``reader=icip2024.DeviceFusedReader`` handed to the same call).  The payloads are uploaded outside the timed span.
+      The ELIC device decode is measured the other way round too: its own fused reader against ``DeviceChainReader``.
 
 Every figure is the median over ``--reps`` runs after ``--warmup`` untimed ones, each run between two HIP events on the stream
 (the host-coded ELIC calls synchronise inside, so their span contains the host's coding time, as a caller sees it).  Prints one
@@ -21,40 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "video-compression_amd"))
 from bench import synthetic_gop  # noqa: E402
-from vcamd import hip, icip2024  # noqa: E402
+from vcamd import icip2024  # noqa: E402
 from vcamd.seeding import seeded_state_dict  # noqa: E402
-
-
-def _fused_uploaded(self, dec, hz, wz, f1d, f2d, f3d, temporal_into, invhypergain, invgain, res, trace):
-    """_Elic._decompress_t_uploaded with ONE vc_irans_decode_gc_ckbd launch per pass in place of the product's three-launch chain:
-    the private switch of this tool (the product keeps the chain: DESIGN.md section 4g)"""
-    L, M, T = hip.lib(), self.M, hip.T
-    dev = self.Gain.device
-    n, h, w = dec.images, 4 * hz, 4 * wz
-    table = self._scale_table_dev()
-    eb_tables, gc_tables = self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()
-    z_sym = dec.decode(self._z_index_dev(n, hz * wz, dev), eb_tables)
-    z_hat = T.empty(n, hz, wz, self.N, dev)
-    hip.check(L.vc_eb_dequant(hip.stream(), z_sym.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(), invhypergain.data_ptr(),
-                              z_hat.view()), "vc_eb_dequant")
-    pin0, pin = self._hyper_buffers(z_hat, temporal_into)
-    y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
-    for i, c0, c1, parity, scales, means in self._group_passes(pin0, pin, y_hat):
-        dec.decode_gc_ckbd(gc_tables, scales, means, parity, table, None, y_hat.channels(c0, c1))
-    return self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
-
-
-def _chain(self, tables, scales, means, parity, scale_table, out_gain, y_hat, symbols_out=None):
-    """IransDecoder.decode_gc_ckbd as the three-launch chain with its two scratch tensors: what the device-coded I-frame decode would
-    cost on the B-frame decoders' chain (second private switch of this tool)"""
-    L = hip.lib()
-    idx = torch.empty((self.images, y_hat.c * y_hat.h * (y_hat.w // 2)), dtype=torch.int32, device=self.buf.device)
-    hip.check(L.vc_gc_indexes_ckbd(hip.stream(), scales.view(), parity, scale_table.data_ptr(), scale_table.numel(), idx.data_ptr()),
-              "vc_gc_indexes_ckbd")
-    sym = self.decode(idx, tables)
-    hip.check(L.vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None if out_gain is None else out_gain.data_ptr(), parity,
-                                   y_hat.view()), "vc_gc_dequant_ckbd")
-    return y_hat
 
 
 def median_ms(fn, warmup, reps, setup=None):
@@ -100,16 +69,12 @@ def main():
         def upload():
             return model.upload_payloads(enc["strings"], args.waves)
 
-        def decode(decoders):
-            decode.x_hat = model.decompress(x1, x2, 0.5, 0.5, decoders, enc["shape"], args.s, dr, coder="device", waves=args.waves)["x_hat"]
+        def decode(decoders, reader=None):
+            decode.x_hat = model.decompress(x1, x2, 0.5, 0.5, decoders, enc["shape"], args.s, dr, coder="device", waves=args.waves,
+                                            reader=reader)["x_hat"]
         chain = median_ms(decode, args.warmup, args.reps, upload)
         same = bool(torch.equal(decode.x_hat, enc["x_hat"]))
-        real = icip2024._Elic._decompress_t_uploaded
-        icip2024._Elic._decompress_t_uploaded = _fused_uploaded
-        try:
-            fused = median_ms(decode, args.warmup, args.reps, upload)
-        finally:
-            icip2024._Elic._decompress_t_uploaded = real
+        fused = median_ms(lambda d: decode(d, icip2024.DeviceFusedReader), args.warmup, args.reps, upload)
         same = same and bool(torch.equal(decode.x_hat, enc["x_hat"]))
         out["b_frame_decompress"] = {"down_ratio": dr, "fused": fused, "chain": chain, "bit_identical": same}
         del model
@@ -129,16 +94,12 @@ def main():
                 res[coder] = {"compress": median_ms(compress, args.warmup, args.reps)}
                 e = coded["enc"]
 
-                def decompress(_):
-                    coded["dec"] = intra.decompress(e["strings"], e["shape"], **kw)
+                def decompress(_, reader=None):
+                    coded["dec"] = intra.decompress(e["strings"], e["shape"], reader=reader, **kw)
                 res[coder]["decompress"] = median_ms(decompress, args.warmup, args.reps)
                 if coder == "device":          # the same decode with the chain in place of the fused kernel
-                    fused_y, real = coded["dec"]["y_hat"], hip.IransDecoder.decode_gc_ckbd
-                    hip.IransDecoder.decode_gc_ckbd = _chain
-                    try:
-                        res[coder]["decompress_on_the_chain"] = median_ms(decompress, args.warmup, args.reps)
-                    finally:
-                        hip.IransDecoder.decode_gc_ckbd = real
+                    fused_y = coded["dec"]["y_hat"]
+                    res[coder]["decompress_on_the_chain"] = median_ms(lambda _: decompress(_, icip2024.DeviceChainReader), args.warmup, args.reps)
                     res[coder]["chain_bit_identical"] = all(bool(torch.equal(a, b)) for a, b in zip(fused_y, coded["dec"]["y_hat"]))
                 strings = e["strings"] if coder == "device" else icip2024._flat_strings(e["strings"])
                 res[coder]["bytes"] = sum(len(b) for b in strings)

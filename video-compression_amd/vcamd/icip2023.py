@@ -18,12 +18,9 @@ Per level one buffer [fref1 | fref2 | fcur] holds what the reference concatenate
 thirds, so no concatenation is launched.  The reference has no compress() for this model; compress / decompress here are the
 twelve strings per frame of FlowGuidedB's format (vcamd/icip2024.py: _Elic.compress_t / decompress_t), without a container.
 """
-import torch.nn as nn
-
 from . import hip, icip2024
 from .hip import T
-from .icip2024 import (DeformConv2d, _flat_strings, deconv, get_order_typ_list, select_references,  # noqa: F401
-                       update_buffer)
+from .icip2024 import DeformConv2d, deconv, get_order_typ_list, select_references, update_buffer  # noqa: F401
 from .layers import BitCounter
 from .lhbdc import _require_frames
 
@@ -71,9 +68,7 @@ class Res_ELIC(icip2024._Elic):
         super().__init__(3, 2, tuple(2 * c for c in CHANS), N, M, chans=CHANS, stem=True)
 
 
-class DeformB(nn.Module):
-    CODERS = ("host", "device")
-
+class DeformB(icip2024._BFrameBitstream):
     def __init__(self):
         super().__init__()
         self.feature_extractor = MS_Feature()
@@ -163,7 +158,7 @@ class DeformB(nn.Module):
                 "size_offset": size_offset, "size_residual": size_res}
 
     # -- real bitstream (FlowGuidedB's strings; the reference has none for this model) ---------------------------------------
-    def _bitstream_pass(self, xref1, xref2, xcur, s, strings=None, shape=None, trace=None, coder="host", waves=4):
+    def _bitstream_pass(self, xref1, xref2, xcur, s, strings=None, shape=None, trace=None, coder="host", waves=4, reader=None):
         """The stages of :meth:`forward_device` with the two compressors on their bitstream paths; ``xcur`` is None on the decoder,
         which runs the reference-only stages through the same launches on the same buffer layouts (the per-level buffers keep
         their fcur slice, unused)."""
@@ -172,32 +167,10 @@ class DeformB(nn.Module):
             raise hip.VcError("frame size must be a multiple of 64 (the reference pads with utils.pad), both references alike")
         F_, fref1, fref2, fcur = self._features(xref1, xref2, xcur)
         cond = [F_[l].channels(0, 2 * CHANS[l]) for l in range(3)]
-        t_off, t_res = ({}, {}) if trace is not None else (None, None)
-        oc, rc = self.offset_compressor, self.residual_compressor
-        off_cond = lambda dst: self.offset_temp_encoder.run(cond[0], cond[1], cond[2], out=dst)  # noqa: E731
-        out = {}
-        if enc:
-            out["offset"] = oc.compress_t([F_[0]], [F_[1]], [F_[2]], cond[0], cond[1], cond[2], off_cond, s, trace=t_off, coder=coder,
-                                          waves=waves)
-            offs = out["offset"]["heads"]
-        else:
-            offs = oc.decompress_t(strings["offset"], shape, cond[0], cond[1], cond[2], off_cond, s, trace=t_off)
-        comp = [self.get_deformed_maps_t(offs[l], fref1[l], fref2[l], l + 1) for l in (2, 1, 0)][::-1]
-        res_cond = lambda dst: self.residual_temp_encoder.run(comp[0], comp[1], comp[2], out=dst)  # noqa: E731
-        if enc:
-            out["residual"] = rc.compress_t([xcur, fcur[0], comp[0]], [fcur[1], comp[1]], [fcur[2], comp[2]], comp[0], comp[1], comp[2],
-                                            res_cond, s, res=tuple(comp), trace=t_res, coder=coder, waves=waves)
-            xs = out["residual"]["heads"]
-        else:
-            xs = rc.decompress_t(strings["residual"], shape, comp[0], comp[1], comp[2], res_cond, s, res=tuple(comp), trace=t_res)
-        if trace is not None:
-            trace.update({"offset": t_off, "residual": t_res})
-        out["x_hat"] = self.reconstructor.run(*xs)
-        return out
-
-    def _check_coder(self, coder, waves):
-        if coder not in self.CODERS or not hip.irans_waves_ok(waves):
-            raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {self.CODERS}, waves a power of two in 1..16")
+        align = lambda offs: [self.get_deformed_maps_t(offs[l], fref1[l], fref2[l], l + 1) for l in (2, 1, 0)][::-1]  # noqa: E731
+        return self._coded_tail(F_ if enc else None, cond, self.offset_temp_encoder, align,
+                                [[xcur, fcur[0]], [fcur[1]], [fcur[2]]] if enc else None, self.residual_temp_encoder, s, strings, shape,
+                                trace, coder, waves, reader)
 
     def compress(self, xref1, xref2, xcur, s, trace=None, coder="host", waves=4):
         """Encode a B-frame for real.  NCHW CUDA tensors as :meth:`forward`.  Returns ``{"strings": {"offset", "residual"} each
@@ -207,58 +180,25 @@ class DeformB(nn.Module):
         explains.  ``coder="device"``: "strings" is ``{"offset": [payload per image], "residual": [...]}`` of the interleaved coder,
         the result gains "coder" and "waves"; x_hat is bit for bit that of the host-coded call."""
         _require_frames(xref1, xref2, xcur)
-        self._check_coder(coder, waves)
-        s = icip2024.FlowGuidedB._coding_level(s)
+        icip2024._check_coder(coder, waves)
+        s = self._coding_level(s)
         with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
             out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), hip.nchw_to_nhwc(xcur), s, trace=trace,
                                        coder=coder, waves=waves)
-            x_hat = hip.nhwc_to_nchw(out["x_hat"])
-        strings = {k: out[k]["strings"] for k in ("offset", "residual")}
-        device = coder == "device"
-        nbytes = sum(len(b) for k in strings for b in (strings[k] if device else _flat_strings(strings[k])))
-        estimate = float((out["offset"]["bits"] + out["residual"]["bits"]).item())
-        result = {"strings": strings, "shape": out["offset"]["shape"], "x_hat": x_hat, "size": 8 * nbytes, "size_estimate": estimate}
-        if device:
-            result.update({"coder": coder, "waves": int(waves)})
-        return result
+        return self._compress_result(out, coder, waves)
 
-    def upload_payloads(self, strings, waves=4):
-        """The payloads of ``compress(coder="device")`` on the device: ``{"offset", "residual"}`` of hip.IransDecoder, which
-        :meth:`decompress` takes in place of the strings; the caller then owns ``finish()`` of both, after it has used x_hat."""
-        self._check_coder("device", waves)
-        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"} or len(strings["offset"]) != len(strings["residual"]) \
-                or not all(isinstance(b, (bytes, bytearray)) for k in strings for b in strings[k]) or not strings["offset"]:
-            raise hip.VcError('strings: {"offset": [payload per image], "residual": [payload per image]}')
-        dev = self.offset_compressor.Gain.device
-        return {k: hip.IransDecoder(strings[k], waves, dev) for k in ("offset", "residual")}
-
-    def decompress(self, xref1, xref2, strings, shape, s, trace=None, coder="host", waves=4):
-        """Decode the strings of :meth:`compress` from the two references alone: ``{"x_hat"}``.  ``coder="device"`` reads the
-        payloads of ``compress(coder="device")`` (one upload, then launches only) and looks at the decoders' error words once, at
-        the end: a damaged payload raises VcError after the reconstruction is enqueued."""
+    def decompress(self, xref1, xref2, strings, shape, s, trace=None, coder="host", waves=4, reader=None):
+        """Decode the strings of :meth:`compress` (or the result of ``upload_payloads``) from the two references alone: ``{"x_hat"}``.
+        ``coder="device"`` reads the payloads of ``compress(coder="device")`` (one upload, then launches only) and looks at the
+        decoders' error words once, at the end: a damaged payload raises VcError after the reconstruction is enqueued.  ``reader``:
+        as FlowGuidedB.decompress."""
         _require_frames(xref1, xref2)
-        self._check_coder(coder, waves)
-        s = icip2024.FlowGuidedB._coding_level(s)
-        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"}:
-            raise hip.VcError('strings: {"offset": ..., "residual": ...}')
-        hz, wz = int(shape[0]), int(shape[1])
-        device = coder == "device"
-        uploaded = device and all(isinstance(v, hip.IransDecoder) for v in strings.values())
-        if device:
-            decoders = strings if uploaded else self.upload_payloads(strings, waves)
-            images = decoders["offset"].images
-            if any(d.images != xref1.shape[0] or d.waves != int(waves) for d in decoders.values()):
-                raise hip.VcError(f"{images} image(s) / waves {waves} do not belong to references {tuple(xref1.shape)} and the payloads")
-            strings = decoders
-        elif len(strings["offset"]) != 2 or len(strings["offset"][1]) != xref1.shape[0]:
-            raise hip.VcError(f"the strings do not hold {xref1.shape[0]} image(s)")
-        if (64 * hz, 64 * wz) != tuple(xref1.shape[2:]):
-            raise hip.VcError(f"hyper-latent shape {hz}x{wz} does not belong to references {tuple(xref1.shape)}")
+        icip2024._check_coder(coder, waves)
+        s = self._coding_level(s)
+        strings, shape, mine = self._decoder_inputs(strings, shape, coder, waves, xref1)
         with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
-            out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), None, s, strings=strings, shape=(hz, wz),
-                                       trace=trace)
-            x_hat = hip.nhwc_to_nchw(out["x_hat"])
-        if device and not uploaded:
-            for d in strings.values():
-                d.finish()
-        return {"x_hat": x_hat}
+            out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), None, s, strings=strings, shape=shape,
+                                       trace=trace, reader=reader)
+        for d in mine:
+            d.finish()
+        return {"x_hat": out["x_hat"]}

@@ -269,11 +269,75 @@ class Reconstuctor(_Seq):
 # compression_bottlenecks.py
 # ------------------------------------------------------------------------------------------------
 GROUPS = (0, 6, 12, 24, 48)
+CODERS = ("host", "device")
+
+
+def _check_coder(coder, waves):
+    if coder not in CODERS or not hip.irans_waves_ok(waves):
+        raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {CODERS}, waves a power of two in 1..16")
+
+
+# ---- the three pass readers of the checkerboard decoder (JointAutoregressiveHierarchicalPriors._decode_passes) ----------------
+# reader(group, parity, scales, means, out): fills the pass's parity of ``out`` (the group's channel window of y_hat) with
+# symbol + mean, the symbols taken from where the reader's coder left them, in the squeezed order vc_gc_forward_ckbd wrote.
+class HostStreamReader:
+    """Host-coded strings: vc_gc_indexes_ckbd -> indexes to the host -> RansStreamDecoder.decode_stream -> symbols back ->
+    vc_gc_dequant_ckbd; one decoder per group string, continued from the anchor pass to the non-anchor pass.  ``groups``: per
+    group the list of its strings -- one per image (``per_image``) or one for the whole call."""
+
+    def __init__(self, model, groups, per_image):
+        self.table, self.tables = model._scale_table_dev(), model.gaussian_conditional.tables()
+        self.groups, self.per_image = groups, per_image
+        self.decoders, self.keep = None, []
+
+    def __call__(self, group, parity, scales, means, out):
+        if parity == 1:
+            self.decoders = [hip.RansStreamDecoder(b) for b in self.groups[group]]
+        idx = torch.empty((out.n, out.c * out.h * (out.w // 2)), dtype=torch.int32, device=out.buf.device)
+        hip.check(hip.lib().vc_gc_indexes_ckbd(hip.stream(), scales.view(), parity, self.table.data_ptr(), self.table.numel(),
+                                               idx.data_ptr()), "vc_gc_indexes_ckbd")
+        rows = idx.cpu().numpy().reshape(out.n if self.per_image else 1, -1)
+        sym = torch.from_numpy(np.stack([d.decode_stream(r, *self.tables) for d, r in zip(self.decoders, rows)])).to(idx.device)
+        self.keep.append(sym)                                          # (must outlive the launch that reads it)
+        hip.check(hip.lib().vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None, parity, out.view()), "vc_gc_dequant_ckbd")
+
+
+class DeviceChainReader:
+    """Uploaded payloads (hip.IransDecoder), three launches per pass: vc_gc_indexes_ckbd -> vc_irans_decode -> vc_gc_dequant_ckbd.
+    Nothing crosses to the host.  The B-frame decoders' reader (the fused launch measured slower there)."""
+
+    def __init__(self, model, dec):
+        self.table, self.tables, self.dec = model._scale_table_dev(), model.gaussian_conditional.irans_tables(), dec
+
+    def __call__(self, group, parity, scales, means, out):
+        idx = torch.empty((out.n, out.c * out.h * (out.w // 2)), dtype=torch.int32, device=out.buf.device)
+        hip.check(hip.lib().vc_gc_indexes_ckbd(hip.stream(), scales.view(), parity, self.table.data_ptr(), self.table.numel(),
+                                               idx.data_ptr()), "vc_gc_indexes_ckbd")
+        sym = self.dec.decode(idx, self.tables)                        # (torch's allocator keeps the block until the stream is past it)
+        hip.check(hip.lib().vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None, parity, out.view()), "vc_gc_dequant_ckbd")
+
+
+class DeviceFusedReader:
+    """Uploaded payloads, one launch per pass: vc_irans_decode_gc_ckbd.  The intra codec's reader."""
+
+    def __init__(self, model, dec):
+        self.table, self.tables, self.dec = model._scale_table_dev(), model.gaussian_conditional.irans_tables(), dec
+
+    def __call__(self, group, parity, scales, means, out):
+        self.dec.decode_gc_ckbd(self.tables, scales, means, parity, self.table, None, out)
 
 
 class JointAutoregressiveHierarchicalPriors(_Seq):
     """Members (and therefore state_dict keys) of compressai.models.JointAutoregressiveHierarchicalPriors(N, M);
-    the ICIP2024 subclasses replace h_a / h_s / entropy_parameters and never run g_a / g_s / context_prediction."""
+    the ICIP2024 subclasses replace h_a / h_s / entropy_parameters and never run g_a / g_s / context_prediction.
+
+    It also holds the ONE walk of the five-group, two-parity checkerboard entropy model both subclasses code with (_Elic: the
+    B-frame compressors, ELIC: the intra codec), parametrised by ``GROUPS`` (the lower channel bounds of the groups):
+    :meth:`_rate_passes` (the rate estimate), :meth:`_passes` (the ten entropy-parameter passes of the bitstream path),
+    :meth:`_encode_passes` and :meth:`_decode_passes` (what fills y_hat pass by pass: vc_gc_forward_ckbd / one of the three
+    readers above).  How the hyper slice gets into the networks' input buffers (pin0, pin) stays with the subclass."""
+    GROUPS = None                      # set by the subclasses
+    STRINGS_PER_IMAGE = True           # host-coded group strings: one per image, or one for the whole call (ELIC, as the reference)
 
     def __init__(self, N=192, M=192):
         super().__init__()
@@ -295,10 +359,159 @@ class JointAutoregressiveHierarchicalPriors(_Seq):
         updated |= self.entropy_bottleneck.update(force=force)
         return updated
 
+    def _bounds(self):
+        return self.GROUPS + (self.M,)
+
+    def _sub(self, name, i, x, **kw):
+        return run_sequential(getattr(self, name)[i], x, self._caches.setdefault(f"{name}.{i}", {}), **kw)
+
+    def _ctx_conv(self, i):
+        key = f"ctx.{i}"
+        if key not in self._caches:
+            self._caches[key] = pack_conv(self.context_prediction_models[i])
+        return self._caches[key]
+
+    def _rate_passes(self, y, pin0, pin, bits, y_hat=None):
+        """The rate estimate of the five groups on (pin0, pin) that already hold the hyper slice: appends 5 x n rows to ``bits``
+        (y_0 .. y_4 of every image) and returns round(y).  The channel context reads round(y) of the groups in front -- or, with
+        ``y_hat`` (forward_stage2; receives round(y - mu) + mu group by group), round(y_hat) of them."""
+        L, M = hip.lib(), self.M
+        y_round = hip.quantize_mask(y)                                 # ste_round(y)
+        y_half = hip.quantize_mask(y, keep_parity=1)                   # anchors only (non-anchors zeroed)
+        bounds = self._bounds()
+        for i in range(5):
+            c0, c1 = bounds[i], bounds[i + 1]
+            p = pin0 if i == 0 else pin
+            ctx = self._ctx_conv(i)(y_half.channels(c0, c1), out=p.channels(0, 2 * M))
+            hip.quantize_mask(ctx, out=ctx, keep_parity=0, do_round=False)
+            if i > 0:
+                prev = y_round.channels(0, c0) if y_hat is None else hip.quantize_mask(y_hat.channels(0, c0))
+                self._sub("channel_context_models", i - 1, prev, out=p.channels(2 * M, 4 * M))
+            gp = self._sub("entropy_parameters", i, p)
+            half = c1 - c0
+            for j in range(y.n):
+                hip.check(L.vc_gc_forward(hip.stream(), y.channels(c0, c1).images(j, j + 1).view(),
+                                          gp.channels(0, half).images(j, j + 1).view(),
+                                          gp.channels(half, 2 * half).images(j, j + 1).view(), None, None,
+                                          hip.NULL_VIEW if y_hat is None else y_hat.channels(c0, c1).images(j, j + 1).view(),
+                                          bits.next_row_ptr(), bits.slots, None, None, None, None, 0, None), "vc_gc_forward")
+        return y_round
+
+    # ---- the walk of the bitstream paths ---------------------------------------------------------------------------------------
+    # One string / segment for the hyper-latents, then per channel group the anchor symbols (checkerboard positions with (row + col)
+    # odd, coded with the checkerboard-context slice at zero) followed by the non-anchor symbols (coded with the checkerboard
+    # context of the just-decoded anchors).  The integers exist in the format's squeezed order only ([n][c][h][w/2], what the
+    # *_ckbd kernels write and read: csrc/entropy.hip): the two passes of a group fill ONE zero-initialised y_hat, no parity mask,
+    # merge or re-ordering in between.  Encoder and decoder walk the one generator: the same launches on the same layouts.
+    def _scale_table_dev(self):
+        gc = self.gaussian_conditional
+        if gc._packed is None:
+            if gc.scale_table.numel() == 0:
+                raise hip.VcError("scale table is empty: call update(force=True) after loading weights")
+            gc._packed = gc.scale_table.detach().float().contiguous().to(gc.scale_bound.device)
+        return gc._packed
+
+    def _z_index_dev(self, n, hw, dev):
+        """table index of every hyper-latent symbol, [n, N * hw] on the device: the channel (no synchronisation)"""
+        return torch.arange(self.N, dtype=torch.int32, device=dev).view(1, self.N, 1).expand(n, self.N, hw).reshape(n, -1).contiguous()
+
+    def _trace_latents(self, trace, y_hat, z_hat):
+        bounds = self._bounds()
+        trace["y_hat"] = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
+        trace["z_hat"] = hip.nhwc_to_nchw(z_hat)
+
+    def _encode_z(self, y, z, bits, out_gain=None):
+        """(z_hat, symbols int32 [n, N * hz * wz]) of the hyper-latents z of the latents y; one row of ``bits``"""
+        if (y.h, y.w) != (4 * z.h, 4 * z.w) or y.w % 2:
+            raise hip.VcError(f"latent {y.h}x{y.w} / hyper-latent {z.h}x{z.w}: the frame must be a multiple of 64")
+        z_hat = T.empty(z.n, z.h, z.w, z.c, z.buf.device)
+        z_sym = torch.empty((z.n, z.c * z.h * z.w), dtype=torch.int32, device=z.buf.device)
+        hip.check(hip.lib().vc_eb_forward(hip.stream(), z.view(), self.entropy_bottleneck.device_params().data_ptr(), None,
+                                          None if out_gain is None else out_gain.data_ptr(), z_hat.view(), z_sym.data_ptr(),
+                                          bits.next_row_ptr(), bits.slots, None), "vc_eb_forward")
+        return z_hat, z_sym
+
+    def _passes(self, pin0, pin, y_hat):
+        """The ten entropy-parameter passes of a frame, in coding order: yields (group, c0, c1, parity, scales, means) with the two
+        Gaussian-parameter views of the pass.  (pin0, pin) = [ctx | hyper] of group 0 and [ctx | channel ctx | hyper] of the others,
+        the hyper slices filled.  The caller fills ``y_hat`` (zero-initialised) at the pass's parity of channels c0:c1 before it
+        asks for the next pass: the non-anchor pass and the later groups read it."""
+        M = self.M
+        bounds = self._bounds()
+        for i in range(5):
+            c0, c1 = bounds[i], bounds[i + 1]
+            cg = c1 - c0
+            p = pin0 if i == 0 else pin
+            hip.axpby(p.channels(p.c - 2 * M, p.c), None, alpha=0.0, out=p.channels(0, 2 * M))   # anchor pass: ctx = 0 (hyper is finite)
+            if i > 0:
+                self._sub("channel_context_models", i - 1, y_hat.channels(0, c0), out=p.channels(2 * M, 4 * M))
+            for parity in (1, 0):
+                if parity == 0:                    # the group's anchors are in y_hat, its non-anchors still zero
+                    self._ctx_conv(i)(y_hat.channels(c0, c1), out=p.channels(0, 2 * M))
+                gp = self._sub("entropy_parameters", i, p)
+                yield i, c0, c1, parity, gp.channels(0, cg), gp.channels(cg, 2 * cg)
+
+    def _zero_latents(self, pin):
+        n, h, w, M = pin.n, pin.h, pin.w, self.M
+        return T(torch.zeros(n * h * w * M, dtype=torch.float32, device=pin.buf.device), n, h, w, M, h * w * M, w * M, M)
+
+    def _encode_passes(self, y, pin0, pin, bits, passes=None):
+        """Encoder body: (y_hat, coded) with ``coded`` the segment table of the ten passes, (symbols, indexes) int32 device tensors
+        [n, count] in squeezed order; one row of ``bits`` per pass.  ``passes`` (a list): receives per pass a dict group / c0 / c1 /
+        parity / y / scales / means of views."""
+        table = self._scale_table_dev()
+        y_hat, coded = self._zero_latents(pin), []
+        for i, c0, c1, parity, scales, means in self._passes(pin0, pin, y_hat):
+            sym = torch.empty((y.n, (c1 - c0) * y.h * (y.w // 2)), dtype=torch.int32, device=y.buf.device)
+            idx = torch.empty_like(sym)
+            hip.check(hip.lib().vc_gc_forward_ckbd(hip.stream(), y.channels(c0, c1).view(), scales.view(), means.view(), None, None,
+                                                   y_hat.channels(c0, c1).view(), parity, bits.next_row_ptr(), bits.slots,
+                                                   sym.data_ptr(), idx.data_ptr(), table.data_ptr(), table.numel()), "vc_gc_forward_ckbd")
+            coded.append((sym, idx))
+            if passes is not None:
+                passes.append({"group": i, "c0": c0, "c1": c1, "parity": parity, "y": y.channels(c0, c1), "scales": scales, "means": means})
+        return y_hat, coded
+
+    def _decode_passes(self, pin0, pin, reader):
+        """Decoder body: y_hat, every pass filled by ``reader`` (one of the three pass readers)"""
+        y_hat = self._zero_latents(pin)
+        for i, c0, c1, parity, scales, means in self._passes(pin0, pin, y_hat):
+            reader(i, parity, scales, means, y_hat.channels(c0, c1))
+        return y_hat
+
+    def _code_strings(self, z_sym, coded, coder, waves, trace):
+        """The strings of a call from its segment table (z, then the ten passes of :meth:`_encode_passes`); ``trace`` receives the
+        table as "coded", (symbols, indexes) per segment.
+        ``coder="device"``: one payload of the interleaved coder per image -- the hyper-latent segment (table set 0, index =
+        channel), then the ten passes (table set 1) -- from one launch of vc_irans_encode on the integers where they lie;
+        collecting the payloads is the one synchronisation.
+        ``coder="host"``: [[g0 strings], ..., [g4 strings]], [z string per image]] of the sequential coder; a group string holds the
+        anchor integers, then the non-anchor integers -- of one image each (``STRINGS_PER_IMAGE``) or of all images of the call.
+        The only device -> host traffic of the encoder: squeezed int32 tensors (one synchronisation, after the last launch)."""
+        device = coder == "device"
+        if device or trace is not None:
+            table = [(z_sym, self._z_index_dev(z_sym.shape[0], z_sym.shape[1] // self.N, z_sym.device))] + coded
+            if trace is not None:
+                trace["coded"] = table
+        if device:
+            return hip.irans_encode([(sym, idx, int(k > 0)) for k, (sym, idx) in enumerate(table)],
+                                    [self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()], waves)
+        gc_tables = self.gaussian_conditional.tables()
+        z_index = np.repeat(np.arange(self.N, dtype=np.int32), z_sym.shape[1] // self.N)
+        z_strings = [hip.rans_encode(row, z_index, *self.entropy_bottleneck.tables()) for row in z_sym.cpu().numpy()]
+        rows = z_sym.shape[0] if self.STRINGS_PER_IMAGE else 1
+        strings = []
+        for g in range(5):
+            host = [(sym.cpu().numpy().reshape(rows, -1), idx.cpu().numpy().reshape(rows, -1)) for sym, idx in coded[2 * g:2 * g + 2]]
+            strings.append([hip.rans_encode(np.concatenate([sy[j] for sy, _ in host]), np.concatenate([ix[j] for _, ix in host]),
+                                            *gc_tables) for j in range(rows)])
+        return [strings, z_strings]
+
 
 class _Elic(JointAutoregressiveHierarchicalPriors):
     """Body shared by Offset_ELIC (enc_mult 5, dec_mult 4, three 432-channel offset heads) and Res_ELIC
     (enc_mult 2, dec_mult 1, residual heads of 64/96/128 channels)."""
+    GROUPS = GROUPS
 
     def __init__(self, enc_mult, dec_mult, outs, N=128, M=128, chans=(64, 96, 128), stem=False):
         """``chans``: widths of the three feature levels the multipliers count in.  ``stem`` (ICIP2023's Res_ELIC): a g_a0 stage
@@ -378,16 +591,6 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
             self._gain_cache[s] = tuple(out)
         return self._gain_cache[s]
 
-    def _sub(self, name, i, x, **kw):
-        seq = getattr(self, name)[i]
-        return run_sequential(seq, x, self._caches.setdefault(f"{name}.{i}", {}), **kw)
-
-    def _ctx_conv(self, i):
-        key = f"ctx.{i}"
-        if key not in self._caches:
-            self._caches[key] = pack_conv(self.context_prediction_models[i])
-        return self._caches[key]
-
     def _analysis(self, enc1, enc2, enc3):
         """g_a1 .. g_a3 (behind g_a0 where the codec has one) on the lists of views whose concatenation the reference feeds them"""
         if self.stem:
@@ -408,55 +611,25 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         move them in place -- teacher forcing for stage-wise parity checks on checkpoints whose latents sit next to rounding boundaries.
         Appends 6 x n rows to ``bits`` (n = batch size): z of every image, then y_0 .. y_4 of every image."""
         L = hip.lib()
-        M = self.M
         gain, hypergain, invhypergain, invgain = self.interpolate_gain(s)
         y = self._analysis(enc1, enc2, enc3)
-        dev, n, h, w = y.buf.device, y.n, y.h, y.w
         y = hip.channel_scale(y, gain, out=y)
         z = self.seq("h_a", y, final_chscale=hypergain)
         if force is not None:
             force("y", y)
             force("z", z)
-        for i in range(n):                                           # one counter row per image and tensor
+        for i in range(y.n):                                         # one counter row per image and tensor
             hip.check(L.vc_eb_forward(hip.stream(), z.images(i, i + 1).view(), self.entropy_bottleneck.device_params().data_ptr(),
                                       None, None, hip.NULL_VIEW, None, bits.next_row_ptr(), bits.slots, None), "vc_eb_forward")
         z_hat = hip.quantize_mask(z, gain=invhypergain)
-        fusion_in = T.empty(n, h, w, 2 * M, dev)                       # [h_s(z_hat) | temporal condition]
-        self.seq("h_s", z_hat, out=fusion_in.channels(0, M))
-        temporal_into(fusion_in.channels(M, 2 * M))
-        params_in = T.empty(n, h, w, 6 * M, dev)                       # [ctx | channel ctx | hyper]
-        hyper = self.seq("prior_fusion", fusion_in, out=params_in.channels(4 * M, 6 * M))
-        params_in0 = T.empty(n, h, w, 4 * M, dev)                      # group 0 has no channel context: [ctx | hyper]
-        hip.axpby(hyper, None, out=params_in0.channels(2 * M, 4 * M))
+        pin0, pin = self._hyper_buffers(z_hat, temporal_into)
         if trace is not None:
             trace.update({"y": y, "z": z})
-        y_round = hip.quantize_mask(y)                                 # ste_round(y)
-        y_half = hip.quantize_mask(y, keep_parity=1)                   # anchors only (non-anchors zeroed)
-        bounds = GROUPS + (M,)
-        for i in range(5):
-            c0, c1 = bounds[i], bounds[i + 1]
-            pin = params_in0 if i == 0 else params_in
-            ctx = self._ctx_conv(i)(y_half.channels(c0, c1), out=pin.channels(0, 2 * M))
-            hip.quantize_mask(ctx, out=ctx, keep_parity=0, do_round=False)
-            if i > 0:
-                self._sub("channel_context_models", i - 1, y_round.channels(0, c0), out=pin.channels(2 * M, 4 * M))
-            gp = self._sub("entropy_parameters", i, pin)
-            half = (c1 - c0)
-            for j in range(n):
-                hip.check(L.vc_gc_forward(hip.stream(), y.channels(c0, c1).images(j, j + 1).view(),
-                                          gp.channels(0, half).images(j, j + 1).view(),
-                                          gp.channels(half, 2 * half).images(j, j + 1).view(), None, None, hip.NULL_VIEW,
-                                          bits.next_row_ptr(), bits.slots, None, None, None, None, 0, None), "vc_gc_forward")
-        y_hat = hip.quantize_mask(y, gain=invgain)
-        xhat3 = self.seq("g_s3", y_hat)
-        head3 = self._head("g_o3", [xhat3, f3d], res[2])
-        xhat2 = self.seq_cat("g_s2", [xhat3, f3d])
-        head2 = self._head("g_o2", [xhat2, f2d], res[1])
-        xhat1 = self.seq_cat("g_s1", [xhat2, f2d])
-        head1 = self._head("g_o1", [xhat1, f1d], res[0])
+        self._rate_passes(y, pin0, pin, bits)
+        heads = self._synthesis_heads(hip.quantize_mask(y, gain=invgain), f1d, f2d, f3d, res)
         if trace is not None:
-            trace["heads"] = (head1, head2, head3)
-        return head1, head2, head3
+            trace["heads"] = heads
+        return heads
 
     def _head(self, name, parts, res):
         t = self.seq_cat(name, parts)
@@ -465,27 +638,15 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         return hip.axpby(t, res, out=t)
 
     # ---- real bitstream ------------------------------------------------------------------------------------------------------
-    # The reference only estimates this model's rate; the format below is this project's own and follows
-    # the intra codec's conventions (ELIC.compress / decompress): one string for the hyper-latents and ONE string per channel
-    # group, the anchor symbols (checkerboard positions with (row + col) odd, coded with the checkerboard-context slice at zero)
-    # followed by the non-anchor symbols (coded with the checkerboard context of the just-decoded anchors); per image of the
-    # batch its own strings.  Coded values: z symbols = round(z * hypergain - median), z_hat = (symbol + median) * invhypergain;
-    # y symbols = round(y * gain - mu), decoder-side latents round(y - mu) + mu in the gained domain (what the channel and
-    # checkerboard contexts read), synthesis and heads read them times invgain.  The integers cross to and from the host in the
-    # format's squeezed order only (vc_gc_forward_ckbd / vc_gc_indexes_ckbd / vc_gc_dequant_ckbd): the two passes of a group fill
-    # ONE y_hat tensor, no parity mask, merge or numpy re-ordering in between.
-    def _scale_table_dev(self):
-        gc = self.gaussian_conditional
-        if gc._packed is None:
-            if gc.scale_table.numel() == 0:
-                raise hip.VcError("scale table is empty: call update(force=True) after loading weights")
-            gc._packed = gc.scale_table.detach().float().contiguous().to(gc.scale_bound.device)
-        return gc._packed
-
+    # The reference only estimates this model's rate; the format is this project's own and follows the intra
+    # codec's conventions -- the walk of the base class -- with per image of the batch its own strings.  Coded values: z symbols =
+    # round(z * hypergain - median), z_hat = (symbol + median) * invhypergain; y symbols = round(y * gain - mu), decoder-side latents
+    # round(y - mu) + mu in the gained domain (what the channel and checkerboard contexts read), synthesis and heads read them times
+    # invgain.
     def _hyper_buffers(self, z_hat, temporal_into):
         """hyper = prior_fusion([h_s(z_hat) | temporal condition]) in the inputs of the entropy-parameter networks: (pin0, pin) =
-        [ctx | hyper] of group 0 and [ctx | channel ctx | hyper] of the others.  Encoder and decoder build them through this one
-        function: the same launches on the same layouts."""
+        [ctx | hyper] of group 0 and [ctx | channel ctx | hyper] of the others.  Rate estimate, encoder and decoder build them
+        through this one function: the same launches on the same layouts."""
         M = self.M
         dev, n, h, w = z_hat.buf.device, z_hat.n, 4 * z_hat.h, 4 * z_hat.w
         fusion_in = T.empty(n, h, w, 2 * M, dev)                       # [h_s(z_hat) | temporal condition]
@@ -497,27 +658,8 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         hip.axpby(hyper, None, out=pin0.channels(2 * M, 4 * M))
         return pin0, pin
 
-    def _group_passes(self, pin0, pin, y_hat):
-        """The ten entropy-parameter passes of a frame, in coding order: yields (group, c0, c1, parity, scales, means) with the two
-        Gaussian-parameter views of the pass.  The caller fills ``y_hat`` (zero-initialised, gained domain) at the pass's parity of
-        channels c0:c1 before it asks for the next pass: the non-anchor pass and the later groups read it."""
-        M = self.M
-        bounds = GROUPS + (M,)
-        for i in range(5):
-            c0, c1 = bounds[i], bounds[i + 1]
-            cg = c1 - c0
-            p = pin0 if i == 0 else pin
-            hip.axpby(p.channels(p.c - 2 * M, p.c), None, alpha=0.0, out=p.channels(0, 2 * M))   # anchor pass: ctx = 0 (hyper is finite)
-            if i > 0:
-                self._sub("channel_context_models", i - 1, y_hat.channels(0, c0), out=p.channels(2 * M, 4 * M))
-            for parity in (1, 0):
-                if parity == 0:                    # the group's anchors are in y_hat, its non-anchors still zero
-                    self._ctx_conv(i)(y_hat.channels(c0, c1), out=p.channels(0, 2 * M))
-                gp = self._sub("entropy_parameters", i, p)
-                yield i, c0, c1, parity, gp.channels(0, cg), gp.channels(cg, 2 * cg)
-
-    def _synthesis_heads(self, y_hat, invgain, f1d, f2d, f3d, res):
-        y_syn = hip.channel_scale(y_hat, invgain)
+    def _synthesis_heads(self, y_syn, f1d, f2d, f3d, res):
+        """the three decoder heads from the latents the synthesis reads (inverse gain applied)"""
         xhat3 = self.seq("g_s3", y_syn)
         head3 = self._head("g_o3", [xhat3, f3d], res[2])
         xhat2 = self.seq_cat("g_s2", [xhat3, f3d])
@@ -526,15 +668,6 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         head1 = self._head("g_o1", [xhat1, f1d], res[0])
         return head1, head2, head3
 
-    def _trace_latents(self, trace, y_hat, z_hat):
-        bounds = GROUPS + (self.M,)
-        trace["y_hat"] = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
-        trace["z_hat"] = hip.nhwc_to_nchw(z_hat)
-
-    def _z_index_dev(self, n, hw, dev):
-        """table index of every hyper-latent symbol, [n, N * hw] on the device: the channel (no synchronisation)"""
-        return torch.arange(self.N, dtype=torch.int32, device=dev).view(1, self.N, 1).expand(n, self.N, hw).reshape(n, -1).contiguous()
-
     def compress_t(self, enc1, enc2, enc3, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None, coder="host", waves=4):
         """Encoder of the bitstream path on channels-last views (arguments as :meth:`code`).  Returns ``{"strings": [[[g0 per
         image], ..., [g4 per image]], [z per image]], "shape": (hz, wz), "heads": the three decoder heads computed from the y_hat
@@ -542,131 +675,52 @@ class _Elic(JointAutoregressiveHierarchicalPriors):
         z row + two parity rows per group)}``.  ``trace``: receives "y_hat" (five NCHW tensors, gained domain), "z_hat" and
         "passes" (per pass a dict group / c0 / c1 / parity / y / scales / means of views) and "coded" (the segment table: (symbols,
         indexes) int32 device tensors [n, count] of z and of the ten passes in coding order).  ``coder="device"``: "strings" is
-        one payload per image of the interleaved coder instead (hyper-latent segment, then the ten passes),
-        coded by one launch of vc_irans_encode on the integers where they lie."""
-        L, M = hip.lib(), self.M
+        one payload per image of the interleaved coder instead (:meth:`_code_strings`)."""
         gain, hypergain, invhypergain, invgain = self.interpolate_gain(s)
         y = self._analysis(enc1, enc2, enc3)
-        dev, n, h, w = y.buf.device, y.n, y.h, y.w
         y = hip.channel_scale(y, gain, out=y)
         z = self.seq("h_a", y, final_chscale=hypergain)
-        if (h, w) != (4 * z.h, 4 * z.w) or w % 2:
-            raise hip.VcError(f"latent {h}x{w} / hyper-latent {z.h}x{z.w}: the frame must be a multiple of 64")
-        bits = BitCounter(dev, max_rows=11)
-        table = self._scale_table_dev()
-        z_hat = T.empty(n, z.h, z.w, z.c, dev)
-        z_sym = torch.empty((n, z.c * z.h * z.w), dtype=torch.int32, device=dev)
-        hip.check(L.vc_eb_forward(hip.stream(), z.view(), self.entropy_bottleneck.device_params().data_ptr(), None,
-                                  invhypergain.data_ptr(), z_hat.view(), z_sym.data_ptr(), bits.next_row_ptr(), bits.slots, None),
-                  "vc_eb_forward")
+        bits = BitCounter(y.buf.device, max_rows=11)
+        z_hat, z_sym = self._encode_z(y, z, bits, invhypergain)
         pin0, pin = self._hyper_buffers(z_hat, temporal_into)
-        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
-        coded = [[] for _ in range(5)]                                 # per group the (symbols, indexes) of its two passes
         if trace is not None:
             trace["passes"] = []
-        for i, c0, c1, parity, scales, means in self._group_passes(pin0, pin, y_hat):
-            sym = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
-            idx = torch.empty_like(sym)
-            hip.check(L.vc_gc_forward_ckbd(hip.stream(), y.channels(c0, c1).view(), scales.view(), means.view(), None, None,
-                                           y_hat.channels(c0, c1).view(), parity, bits.next_row_ptr(), bits.slots, sym.data_ptr(),
-                                           idx.data_ptr(), table.data_ptr(), table.numel()), "vc_gc_forward_ckbd")
-            coded[i].append((sym, idx))
-            if trace is not None:
-                trace["passes"].append({"group": i, "c0": c0, "c1": c1, "parity": parity, "y": y.channels(c0, c1), "scales": scales,
-                                        "means": means})
-        heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
+        y_hat, coded = self._encode_passes(y, pin0, pin, bits, None if trace is None else trace["passes"])
+        heads = self._synthesis_heads(hip.channel_scale(y_hat, invgain), f1d, f2d, f3d, res)
         total = bits.totals().sum()
-        device = coder == "device"
-        z_index_dev = self._z_index_dev(n, z.h * z.w, dev) if device or trace is not None else None
         if trace is not None:
             self._trace_latents(trace, y_hat, z_hat)
             trace["heads"] = heads
-            trace["coded"] = [(z_sym, z_index_dev)] + [p for passes in coded for p in passes]
-        if device:
-            segments = [(z_sym, z_index_dev, 0)] + [(sym, idx, 1) for passes in coded for sym, idx in passes]
-            payloads = hip.irans_encode(segments, [self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()], waves)
-            return {"strings": payloads, "shape": (z.h, z.w), "heads": heads, "bits": total}
-        # the only device -> host traffic of the pass: squeezed int32 tensors (one synchronisation, after the last launch)
-        eb_tables = self.entropy_bottleneck.tables()
-        gc_tables = self.gaussian_conditional.tables()
-        z_index = np.repeat(np.arange(z.c, dtype=np.int32), z.h * z.w)
-        z_strings = [hip.rans_encode(row, z_index, *eb_tables) for row in z_sym.cpu().numpy()]
-        strings = []
-        for passes in coded:
-            host = [(sym.cpu().numpy(), idx.cpu().numpy()) for sym, idx in passes]
-            strings.append([hip.rans_encode(np.concatenate([sy[j] for sy, _ in host]), np.concatenate([ix[j] for _, ix in host]),
-                                            *gc_tables) for j in range(n)])
-        return {"strings": [strings, z_strings], "shape": (z.h, z.w), "heads": heads, "bits": total}
+        return {"strings": self._code_strings(z_sym, coded, coder, waves, trace), "shape": (z.h, z.w), "heads": heads, "bits": total}
 
-    def decompress_t(self, strings, shape, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None):
-        """Decoder of :meth:`compress_t`: decoder-side inputs only.  Returns the three heads.  Two decode_stream calls per group
-        string on one RansStreamDecoder per image."""
-        L, M = hip.lib(), self.M
+    def decompress_t(self, strings, shape, f1d, f2d, f3d, temporal_into, s, res=(None, None, None), trace=None, reader=None):
+        """Decoder of :meth:`compress_t`: decoder-side inputs only.  Returns the three heads.  ``strings``: the host-coded lists
+        (HostStreamReader: two decode_stream calls per group string on one RansStreamDecoder per image) or the payloads of
+        ``coder="device"``, already uploaded (hip.IransDecoder): nothing crosses to the host, the caller reads the decoder's error
+        words once, after the reconstruction.  ``reader``: the pass reader of uploaded payloads, DeviceChainReader unless given."""
         dev = self.Gain.device
         _, _, invhypergain, invgain = self.interpolate_gain(s)
         hz, wz = int(shape[0]), int(shape[1])
-        if isinstance(strings, hip.IransDecoder):
-            return self._decompress_t_uploaded(strings, hz, wz, f1d, f2d, f3d, temporal_into, invhypergain, invgain, res, trace)
-        if len(strings) != 2 or len(strings[0]) != 5 or not strings[1] or any(len(g) != len(strings[1]) for g in strings[0]):
+        uploaded = isinstance(strings, hip.IransDecoder)
+        if not uploaded and (len(strings) != 2 or len(strings[0]) != 5 or not strings[1] or any(len(g) != len(strings[1]) for g in strings[0])):
             raise hip.VcError("strings: [[g0, ..., g4], z] with one byte string per image in each of the six lists")
         if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
             raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
-        n = len(strings[1])
-        h, w = 4 * hz, 4 * wz
-        table = self._scale_table_dev()
-        eb_tables = self.entropy_bottleneck.tables()
-        gc_tables = self.gaussian_conditional.tables()
-        z_index = np.repeat(np.arange(self.N, dtype=np.int32), hz * wz)
-        z_sym = torch.from_numpy(np.stack([hip.rans_decode(strings[1][j], z_index, *eb_tables) for j in range(n)])).to(dev)
+        if uploaded:
+            n = strings.images
+            z_sym = strings.decode(self._z_index_dev(n, hz * wz, dev), self.entropy_bottleneck.irans_tables())
+            reader = (reader or DeviceChainReader)(self, strings)
+        else:
+            n = len(strings[1])
+            z_index = np.repeat(np.arange(self.N, dtype=np.int32), hz * wz)
+            z_sym = torch.from_numpy(np.stack([hip.rans_decode(b, z_index, *self.entropy_bottleneck.tables()) for b in strings[1]])).to(dev)
+            reader = HostStreamReader(self, strings[0], self.STRINGS_PER_IMAGE)
         z_hat = T.empty(n, hz, wz, self.N, dev)
-        hip.check(L.vc_eb_dequant(hip.stream(), z_sym.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
-                                  invhypergain.data_ptr(), z_hat.view()), "vc_eb_dequant")
+        hip.check(hip.lib().vc_eb_dequant(hip.stream(), z_sym.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
+                                          invhypergain.data_ptr(), z_hat.view()), "vc_eb_dequant")
         pin0, pin = self._hyper_buffers(z_hat, temporal_into)
-        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
-        decoders, keep = None, []
-        for i, c0, c1, parity, scales, means in self._group_passes(pin0, pin, y_hat):
-            if parity == 1:
-                decoders = [hip.RansStreamDecoder(strings[0][i][j]) for j in range(n)]
-            idx = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
-            hip.check(L.vc_gc_indexes_ckbd(hip.stream(), scales.view(), parity, table.data_ptr(), table.numel(), idx.data_ptr()),
-                      "vc_gc_indexes_ckbd")
-            idx_host = idx.cpu().numpy()
-            sym = torch.from_numpy(np.stack([decoders[j].decode_stream(idx_host[j], *gc_tables) for j in range(n)])).to(dev)
-            keep.append(sym)                                           # (must outlive the launch that reads it)
-            hip.check(L.vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None, parity, y_hat.channels(c0, c1).view()),
-                      "vc_gc_dequant_ckbd")
-        heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
-        if trace is not None:
-            self._trace_latents(trace, y_hat, z_hat)
-            trace["heads"] = heads
-        return heads
-
-    def _decompress_t_uploaded(self, dec, hz, wz, f1d, f2d, f3d, temporal_into, invhypergain, invgain, res, trace):
-        """decompress_t on the payloads of ``coder="device"``, already uploaded (hip.IransDecoder): every pass is vc_gc_indexes_ckbd ->
-        vc_irans_decode -> vc_gc_dequant_ckbd on the device, nothing crosses to the host (the caller reads the decoder's error
-        words once, after the reconstruction).  The fused vc_irans_decode_gc_ckbd measured slower than this chain here (DESIGN.md section
-        4g), so the B-frame decoders stay on the chain."""
-        L, M = hip.lib(), self.M
-        dev = self.Gain.device
-        if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
-            raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
-        n, h, w = dec.images, 4 * hz, 4 * wz
-        table = self._scale_table_dev()
-        eb_tables, gc_tables = self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()
-        z_sym = dec.decode(self._z_index_dev(n, hz * wz, dev), eb_tables)
-        z_hat = T.empty(n, hz, wz, self.N, dev)
-        hip.check(L.vc_eb_dequant(hip.stream(), z_sym.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
-                                  invhypergain.data_ptr(), z_hat.view()), "vc_eb_dequant")
-        pin0, pin = self._hyper_buffers(z_hat, temporal_into)
-        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
-        for i, c0, c1, parity, scales, means in self._group_passes(pin0, pin, y_hat):
-            idx = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
-            hip.check(L.vc_gc_indexes_ckbd(hip.stream(), scales.view(), parity, table.data_ptr(), table.numel(), idx.data_ptr()),
-                      "vc_gc_indexes_ckbd")
-            sym = dec.decode(idx, gc_tables)                           # (torch's allocator keeps the block until the stream is past it)
-            hip.check(L.vc_gc_dequant_ckbd(hip.stream(), sym.data_ptr(), means.view(), None, parity, y_hat.channels(c0, c1).view()),
-                      "vc_gc_dequant_ckbd")
-        heads = self._synthesis_heads(y_hat, invgain, f1d, f2d, f3d, res)
+        y_hat = self._decode_passes(pin0, pin, reader)
+        heads = self._synthesis_heads(hip.channel_scale(y_hat, invgain), f1d, f2d, f3d, res)
         if trace is not None:
             self._trace_latents(trace, y_hat, z_hat)
             trace["heads"] = heads
@@ -730,6 +784,8 @@ ELIC_GROUPS = (0, 16, 32, 64, 128)
 class ELIC(JointAutoregressiveHierarchicalPriors):
     """elic.py:85-596: forward (rate estimate, what utils.image_compress calls for the I-frames), forward_stage2, and the
     two-pass checkerboard bitstream codec compress / decompress."""
+    GROUPS = ELIC_GROUPS
+    STRINGS_PER_IMAGE = False
 
     def __init__(self, N=192, M=320, **kwargs):
         super().__init__(N, M)
@@ -754,9 +810,6 @@ class ELIC(JointAutoregressiveHierarchicalPriors):
             CheckerboardContext(in_channels=cin, out_channels=M * 2, kernel_size=5, stride=1, padding=2)
             for cin in [16, 16, 32, 64, M - 128])
 
-    def _sub(self, name, i, x, **kw):
-        return run_sequential(getattr(self, name)[i], x, self._caches.setdefault(f"{name}.{i}", {}), **kw)
-
     def forward_device(self, x, bits, stage2=False):
         """x: T [n,H,W,3] (H, W multiples of 64) -> x_hat T; appends 6 x n rows to ``bits`` (z, y_0..y_4 per image).
         ``stage2`` = forward_stage2 (elic.py:247-305): the channel context sees round(round(y - mu) + mu) of the groups
@@ -772,33 +825,9 @@ class ELIC(JointAutoregressiveHierarchicalPriors):
         hyper = self.seq("h_s", hip.quantize_mask(z), out=params_in.channels(4 * M, 6 * M))
         params_in0 = T.empty(n, h, w, 4 * M, dev)                      # group 0: [ctx | hyper]
         hip.axpby(hyper, None, out=params_in0.channels(2 * M, 4 * M))
-        y_round = hip.quantize_mask(y)
-        y_half = hip.quantize_mask(y, keep_parity=1)
         y_hat = T.empty(n, h, w, M, dev) if stage2 else None            # round(y - mu) + mu, group by group
-        bounds = ELIC_GROUPS + (M,)
-        for i in range(5):
-            c0, c1 = bounds[i], bounds[i + 1]
-            pin = params_in0 if i == 0 else params_in
-            ctx = self._ctx_conv(i)(y_half.channels(c0, c1), out=pin.channels(0, 2 * M))
-            hip.quantize_mask(ctx, out=ctx, keep_parity=0, do_round=False)
-            if i > 0:
-                prev = hip.quantize_mask(y_hat.channels(0, c0)) if stage2 else y_round.channels(0, c0)
-                self._sub("channel_context_models", i - 1, prev, out=pin.channels(2 * M, 4 * M))
-            gp = self._sub("entropy_parameters", i, pin)
-            half = c1 - c0
-            for j in range(n):
-                hip.check(L.vc_gc_forward(hip.stream(), y.channels(c0, c1).images(j, j + 1).view(),
-                                          gp.channels(0, half).images(j, j + 1).view(),
-                                          gp.channels(half, 2 * half).images(j, j + 1).view(), None, None,
-                                          y_hat.channels(c0, c1).images(j, j + 1).view() if stage2 else hip.NULL_VIEW,
-                                          bits.next_row_ptr(), bits.slots, None, None, None, None, 0, None), "vc_gc_forward")
+        y_round = self._rate_passes(y, params_in0, params_in, bits, y_hat)
         return self.seq("g_s", y_hat if stage2 else y_round)
-
-    def _ctx_conv(self, i):
-        key = f"ctx.{i}"
-        if key not in self._caches:
-            self._caches[key] = pack_conv(self.context_prediction_models[i])
-        return self._caches[key]
 
     def forward_stage2(self, x):
         """elic.py:247-305 -- same return structure as forward."""
@@ -807,168 +836,24 @@ class ELIC(JointAutoregressiveHierarchicalPriors):
         x_hat = hip.nhwc_to_nchw(self.forward_device(hip.nchw_to_nhwc(x), bits, stage2=True))
         return {"x_hat": x_hat, "size": bits.totals().sum().float()}
 
-    # ---- real bitstream (elic.py:307-496) --------------------------------------------------------------------------
-    # One string for the hyper-latents + ONE string per channel group: the anchor symbols (checkerboard positions with
-    # (row + col) odd, coded against the hyper / channel context only) followed by the non-anchor symbols (coded with the
-    # checkerboard context of the just-decoded anchors).  The networks run on the device; between the two passes of a
-    # group the integers cross to the host, where the squeezed symbol order of the format is assembled and range-coded.
-    @staticmethod
-    def _squeeze_np(t, anchor):
-        """ckbd_anchor_sequeeze / ckbd_nonanchor_sequeeze (elic.py:498-512) on a [n,c,h,w] array."""
-        out = np.empty(t.shape[:3] + (t.shape[3] // 2,), dtype=t.dtype)
-        if anchor:
-            out[:, :, 0::2, :] = t[:, :, 0::2, 1::2]
-            out[:, :, 1::2, :] = t[:, :, 1::2, 0::2]
-        else:
-            out[:, :, 0::2, :] = t[:, :, 0::2, 0::2]
-            out[:, :, 1::2, :] = t[:, :, 1::2, 1::2]
-        return out
-
-    @staticmethod
-    def _unsqueeze_np(t, anchor):
-        out = np.zeros(t.shape[:3] + (t.shape[3] * 2,), dtype=t.dtype)
-        if anchor:
-            out[:, :, 0::2, 1::2] = t[:, :, 0::2, :]
-            out[:, :, 1::2, 0::2] = t[:, :, 1::2, :]
-        else:
-            out[:, :, 0::2, 0::2] = t[:, :, 0::2, :]
-            out[:, :, 1::2, 1::2] = t[:, :, 1::2, :]
-        return out
-
-    def _param_buffers(self, hyper, n, h, w, dev):
-        """Inputs of the entropy-parameter networks, [ctx | (channel ctx) | hyper]: one pair with the checkerboard context
-        held at zero (anchor pass) and one that receives it (non-anchor pass); group 0 has no channel context."""
+    # ---- real bitstream (elic.py:307-496): the walk of the base class, no gains, no temporal condition ------------------------------
+    # coder="host": the reference's strings -- one z string per image and ONE string per channel group for the whole call (the anchor
+    # integers of all images, then the non-anchor integers).  coder="device" (DESIGN.md section 4g): one payload of the interleaved
+    # coder per image; nothing crosses to the host before the payloads are collected / the error words are read.
+    def _hyper_buffers(self, z_hat):
+        """(pin0, pin) = [ctx | hyper] of group 0 and [ctx | channel ctx | hyper] of the others, hyper = h_s(z_hat) copied into both"""
         M = self.M
-        bufs = {}
-        for tag in ("a0", "n0"):
-            t = T.empty(n, h, w, 4 * M, dev)
-            hip.axpby(hyper, None, out=t.channels(2 * M, 4 * M))
-            bufs[tag] = t
-        for tag in ("a", "n"):
-            t = T.empty(n, h, w, 6 * M, dev)
-            hip.axpby(hyper, None, out=t.channels(4 * M, 6 * M))
-            bufs[tag] = t
-        for tag in ("a0", "a"):
-            zero = bufs[tag].channels(0, 2 * M)
-            hip.axpby(hyper, None, alpha=0.0, out=zero)          # hyper is finite: 0 * hyper = 0
-        return bufs
-
-    def _scale_table_dev(self):
-        gc = self.gaussian_conditional
-        if gc._packed is None:
-            if gc.scale_table.numel() == 0:
-                raise hip.VcError("scale table is empty: call update(force=True) after loading weights")
-            gc._packed = gc.scale_table.detach().float().contiguous().to(gc.scale_bound.device)
-        return gc._packed
-
-    # ---- the same codec with the interleaved coder on the device (coder="device"; DESIGN.md section 4g) -------------------------
-    # One payload per image: the hyper-latent segment (table set 0, index = channel), then the ten passes (table set 1) in coding
-    # order -- group 0 anchors, group 0 non-anchors, ... -- the segment table of _Elic.compress_t.  The two passes of a group fill
-    # ONE zero-initialised y_hat where it lies (vc_gc_forward_ckbd / vc_irans_decode_gc_ckbd): no parity mask, no merge, no numpy
-    # and nothing crosses to the host before the payloads are collected / the error words are read.
-    CODERS = ("host", "device")
-
-    def _check_coder(self, coder, waves):
-        if coder not in self.CODERS or not hip.irans_waves_ok(waves):
-            raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {self.CODERS}, waves a power of two in 1..16")
-
-    def _device_passes(self, hyper, y_hat):
-        """The ten entropy-parameter passes in coding order: yields (group, c0, c1, parity, scales, means).  The caller fills
-        ``y_hat`` (zero-initialised) at the pass's parity of channels c0:c1 before it asks for the next pass.  Encoder and decoder
-        both walk this one generator: the same launches on the same layouts."""
-        M = self.M
+        hyper = self.seq("h_s", z_hat)
         n, h, w, dev = hyper.n, hyper.h, hyper.w, hyper.buf.device
-        pin = T.empty(n, h, w, 6 * M, dev)                             # [ctx | channel ctx | hyper]
+        pin = T.empty(n, h, w, 6 * M, dev)
         hip.axpby(hyper, None, out=pin.channels(4 * M, 6 * M))
-        pin0 = T.empty(n, h, w, 4 * M, dev)                            # group 0: [ctx | hyper]
+        pin0 = T.empty(n, h, w, 4 * M, dev)
         hip.axpby(hyper, None, out=pin0.channels(2 * M, 4 * M))
-        bounds = ELIC_GROUPS + (M,)
-        for i in range(5):
-            c0, c1 = bounds[i], bounds[i + 1]
-            cg = c1 - c0
-            p = pin0 if i == 0 else pin
-            hip.axpby(hyper, None, alpha=0.0, out=p.channels(0, 2 * M))   # anchor pass: ctx = 0 (hyper is finite), as _param_buffers
-            if i > 0:
-                self._sub("channel_context_models", i - 1, y_hat.channels(0, c0), out=p.channels(2 * M, 4 * M))
-            for parity in (1, 0):
-                if parity == 0:                    # the group's anchors are in y_hat, its non-anchors still zero
-                    self._ctx_conv(i)(y_hat.channels(c0, c1), out=p.channels(0, 2 * M))
-                gp = self._sub("entropy_parameters", i, p)
-                yield i, c0, c1, parity, gp.channels(0, cg), gp.channels(cg, 2 * cg)
+        return pin0, pin
 
-    def _trace_device(self, trace, y_hat, z_hat, x_hat):
-        bounds = ELIC_GROUPS + (self.M,)
-        trace["y_hat"] = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
-        trace["z_hat"] = hip.nhwc_to_nchw(z_hat)
-        trace["x_hat"] = x_hat
-
-    def _compress_device(self, x, waves, trace):
-        L, M = hip.lib(), self.M
-        xt = hip.nchw_to_nhwc(x.contiguous().float())
-        y = self.seq("g_a", xt)
-        z = self.seq("h_a", y)
-        dev, n, h, w = y.buf.device, y.n, y.h, y.w
-        if (h, w) != (4 * z.h, 4 * z.w) or w % 2:
-            raise hip.VcError(f"latent {h}x{w} / hyper-latent {z.h}x{z.w}: the frame must be a multiple of 64")
-        bits = BitCounter(dev, max_rows=11)
-        table = self._scale_table_dev()
-        z_hat = T.empty(n, z.h, z.w, z.c, dev)
-        z_sym = torch.empty((n, z.c * z.h * z.w), dtype=torch.int32, device=dev)
-        hip.check(L.vc_eb_forward(hip.stream(), z.view(), self.entropy_bottleneck.device_params().data_ptr(), None, None,
-                                  z_hat.view(), z_sym.data_ptr(), bits.next_row_ptr(), bits.slots, None), "vc_eb_forward")
-        hyper = self.seq("h_s", z_hat)
-        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
-        z_index = torch.arange(z.c, dtype=torch.int32, device=dev).view(1, z.c, 1).expand(n, z.c, z.h * z.w).reshape(n, -1).contiguous()
-        segments = [(z_sym, z_index, 0)]
-        for i, c0, c1, parity, scales, means in self._device_passes(hyper, y_hat):
-            sym = torch.empty((n, (c1 - c0) * h * (w // 2)), dtype=torch.int32, device=dev)
-            idx = torch.empty_like(sym)
-            hip.check(L.vc_gc_forward_ckbd(hip.stream(), y.channels(c0, c1).view(), scales.view(), means.view(), None, None,
-                                           y_hat.channels(c0, c1).view(), parity, bits.next_row_ptr(), bits.slots, sym.data_ptr(),
-                                           idx.data_ptr(), table.data_ptr(), table.numel()), "vc_gc_forward_ckbd")
-            segments.append((sym, idx, 1))
-        x_hat = hip.nhwc_to_nchw(self.seq("g_s", y_hat))
-        total = bits.totals().sum()
-        bounds = ELIC_GROUPS + (M,)
-        groups = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
-        if trace is not None:
-            self._trace_device(trace, y_hat, z_hat, x_hat)
-            trace["coded"] = [(sym, idx) for sym, idx, _ in segments]
-        # the one synchronisation of the pass: the word counts of the payloads, after the last launch
-        payloads = hip.irans_encode(segments, [self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()], waves)
-        return {"strings": payloads, "shape": torch.Size([z.h, z.w]), "y_hat": groups, "x_hat": x_hat, "bits": total, "coder": "device",
-                "waves": int(waves)}
-
-    def _decompress_device(self, strings, shape, waves, trace):
-        M = self.M
-        dev = self.entropy_bottleneck.quantiles.device
-        hz, wz = int(shape[0]), int(shape[1])
-        if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
-            raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
-        uploaded = isinstance(strings, hip.IransDecoder)
-        if not uploaded and not (isinstance(strings, (list, tuple)) and strings and all(isinstance(b, (bytes, bytearray)) for b in strings)):
-            raise hip.VcError('ELIC.decompress(coder="device"): strings is one payload (bytes) per image, as compress(coder="device") '
-                              "returns it -- this looks like the host-coded [[g0, ..., g4], z] lists")
-        dec = strings if uploaded else hip.IransDecoder(strings, waves, dev)
-        if dec.waves != int(waves):
-            raise hip.VcError(f"the uploaded payloads were read with waves {dec.waves}, not {waves}")
-        n, h, w = dec.images, 4 * hz, 4 * wz
-        table = self._scale_table_dev()
-        eb_tables, gc_tables = self.entropy_bottleneck.irans_tables(), self.gaussian_conditional.irans_tables()
-        z_hat = T.empty(n, hz, wz, self.N, dev)
-        dec.decode_eb(eb_tables, self.entropy_bottleneck.device_params(), None, z_hat)
-        hyper = self.seq("h_s", z_hat)
-        y_hat = T(torch.zeros(n * h * w * M, dtype=torch.float32, device=dev), n, h, w, M, h * w * M, w * M, M)
-        for i, c0, c1, parity, scales, means in self._device_passes(hyper, y_hat):
-            dec.decode_gc_ckbd(gc_tables, scales, means, parity, table, None, y_hat.channels(c0, c1))
-        x_hat = hip.nhwc_to_nchw(self.seq("g_s", y_hat))
-        bounds = ELIC_GROUPS + (M,)
-        groups = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
-        if trace is not None:
-            self._trace_device(trace, y_hat, z_hat, x_hat)
-        if not uploaded:                           # the one read, after everything is enqueued
-            dec.finish()
-        return {"x_hat": x_hat, "y_hat": groups}
+    def _nchw_groups(self, y_hat):
+        bounds = self._bounds()
+        return [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
 
     def compress(self, x, coder="host", waves=4, trace=None):
         """{"strings": [[[g0], [g1], [g2], [g3], [g4]], [z]], "shape", "y_hat": 5 NCHW tensors} like elic.py:307-414.
@@ -979,121 +864,79 @@ class ELIC(JointAutoregressiveHierarchicalPriors):
         (device coder): receives "coded" (the segment table: (symbols, indexes) of z and of the ten passes), "y_hat", "z_hat",
         "x_hat".  ``waves`` and ``trace`` belong to the device coder: the host coder ignores the first and refuses the second."""
         _require_frames(x)
-        if coder != "host":
-            self._check_coder(coder, waves)
-            return self._compress_device(x, waves, trace)
-        if trace is not None:
+        device = coder != "host"
+        if device:
+            _check_coder(coder, waves)
+        elif trace is not None:
             raise hip.VcError('ELIC.compress: trace= belongs to coder="device" (the host-coded path returns its latents in "y_hat")')
-        L, M = hip.lib(), self.M
-        xt = hip.nchw_to_nhwc(x.contiguous().float())
-        y = self.seq("g_a", xt)
+        y = self.seq("g_a", hip.nchw_to_nhwc(x.contiguous().float()))
         z = self.seq("h_a", y)
-        dev, n, h, w = y.buf.device, y.n, y.h, y.w
-        eb_cdf, eb_len, eb_off = self.entropy_bottleneck.tables()
-        gc_tables = self.gaussian_conditional.tables()
-        table = self._scale_table_dev()
-        z_hat = T.empty(z.n, z.h, z.w, z.c, dev)
-        z_sym = torch.empty((z.n, z.c * z.h * z.w), dtype=torch.int32, device=dev)
-        hip.check(L.vc_eb_forward(hip.stream(), z.view(), self.entropy_bottleneck.device_params().data_ptr(), None, None,
-                                  z_hat.view(), z_sym.data_ptr(), None, 0, None), "vc_eb_forward")
-        z_index = np.repeat(np.arange(z.c, dtype=np.int32), z.h * z.w)
-        z_strings = [hip.rans_encode(row, z_index, eb_cdf, eb_len, eb_off) for row in z_sym.cpu().numpy()]
-        hyper = self.seq("h_s", z_hat)
-        bufs = self._param_buffers(hyper, n, h, w, dev)
-        y_hat = T.empty(n, h, w, M, dev)
-        bounds = ELIC_GROUPS + (M,)
-        strings = []
-        for i in range(5):
-            c0, c1 = bounds[i], bounds[i + 1]
-            cg = c1 - c0
-            pa, pn = (bufs["a0"], bufs["n0"]) if i == 0 else (bufs["a"], bufs["n"])
-            if i > 0:
-                self._sub("channel_context_models", i - 1, y_hat.channels(0, c0), out=pn.channels(2 * M, 4 * M))
-                hip.axpby(pn.channels(2 * M, 4 * M), None, out=pa.channels(2 * M, 4 * M))
-            syms, idxs, parts = [], [], []
-            for anchor in (True, False):
-                pin = pa if anchor else pn
-                if not anchor:
-                    self._ctx_conv(i)(parts[0], out=pin.channels(0, 2 * M))
-                gp = self._sub("entropy_parameters", i, pin)
-                full = T.empty(n, h, w, cg, dev)
-                sym = torch.empty((n, cg, h, w), dtype=torch.int32, device=dev)
-                idx = torch.empty_like(sym)
-                hip.check(L.vc_gc_forward(hip.stream(), y.channels(c0, c1).view(), gp.channels(0, cg).view(), gp.channels(cg, 2 * cg).view(),
-                                          None, None, full.view(), None, 0, None, sym.data_ptr(), idx.data_ptr(), table.data_ptr(),
-                                          table.numel(), None), "vc_gc_forward")
-                parts.append(hip.quantize_mask(full, keep_parity=1 if anchor else 0, do_round=False))
-                syms.append(self._squeeze_np(sym.cpu().numpy(), anchor).reshape(-1))
-                idxs.append(self._squeeze_np(idx.cpu().numpy(), anchor).reshape(-1))
-            hip.axpby(parts[0], parts[1], out=y_hat.channels(c0, c1))
-            strings.append([hip.rans_encode(np.concatenate(syms), np.concatenate(idxs), *gc_tables)])
-        groups = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
-        return {"strings": [strings, z_strings], "shape": torch.Size([z.h, z.w]), "y_hat": groups}
+        bits = BitCounter(y.buf.device, max_rows=11)
+        z_hat, z_sym = self._encode_z(y, z, bits)
+        pin0, pin = self._hyper_buffers(z_hat)
+        y_hat, coded = self._encode_passes(y, pin0, pin, bits)
+        result = {"shape": torch.Size([z.h, z.w]), "y_hat": self._nchw_groups(y_hat)}
+        if device:
+            x_hat = hip.nhwc_to_nchw(self.seq("g_s", y_hat))
+            result.update({"x_hat": x_hat, "bits": bits.totals().sum(), "coder": "device", "waves": int(waves)})
+            if trace is not None:
+                self._trace_latents(trace, y_hat, z_hat)
+                trace["x_hat"] = x_hat
+        result["strings"] = self._code_strings(z_sym, coded, coder, waves, trace)      # the one synchronisation, after the last launch
+        return result
 
-    def decompress(self, strings, shape, coder="host", waves=4, trace=None):
-        """{"x_hat", "cost_time", "y_hat"} like elic.py:416-496 (two decode_stream calls per group string).
+    def decompress(self, strings, shape, coder="host", waves=4, trace=None, reader=None):
+        """{"x_hat", "cost_time", "y_hat"} like elic.py:416-496 (HostStreamReader: two decode_stream calls per group string).
 
         ``coder="device"`` reads the payloads of ``compress(coder="device")`` (or a hip.IransDecoder that already uploaded them):
         one upload, then launches only, {"x_hat", "y_hat"}; the decoder's error words are read once at the end (VcError) -- by
-        the caller (``finish()``) when it handed in the uploaded decoder.  ``trace``: receives "y_hat", "z_hat", "x_hat"."""
+        the caller (``finish()``) when it handed in the uploaded decoder.  ``trace``: receives "y_hat", "z_hat", "x_hat".
+        ``reader``: the pass reader of the payloads, DeviceFusedReader unless given."""
         import time
-        if coder != "host":
-            self._check_coder(coder, waves)
-            return self._decompress_device(strings, shape, waves, trace)
-        if trace is not None:
-            raise hip.VcError('ELIC.decompress: trace= belongs to coder="device" (the host-coded path returns its latents in "y_hat")')
-        if isinstance(strings, hip.IransDecoder) or len(strings) != 2 or len(strings[0]) != 5 or \
-                not all(isinstance(g, (list, tuple)) for g in list(strings[0]) + [strings[1]]):
-            raise hip.VcError('ELIC.decompress(coder="host"): strings is [[g0, ..., g4], z] with one byte string per image in each list '
-                              '-- pass coder="device" for the payloads of compress(coder="device")')
-        t0 = time.process_time()
-        L, M = hip.lib(), self.M
         dev = self.entropy_bottleneck.quantiles.device
-        hz, wz = int(shape[0]), int(shape[1])
-        n = len(strings[1])
-        eb_cdf, eb_len, eb_off = self.entropy_bottleneck.tables()
-        gc_tables = self.gaussian_conditional.tables()
-        table = self._scale_table_dev()
-        z_index = np.repeat(np.arange(self.N, dtype=np.int32), hz * wz)
-        z_sym = np.stack([hip.rans_decode(strings[1][k], z_index, eb_cdf, eb_len, eb_off) for k in range(n)])
-        z_hat = T.empty(n, hz, wz, self.N, dev)
-        z_sym_d = torch.from_numpy(z_sym).to(dev)       # (bound to a local: must outlive the launch that reads it)
-        hip.check(L.vc_eb_dequant(hip.stream(), z_sym_d.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
-                                  None, z_hat.view()), "vc_eb_dequant")
-        hyper = self.seq("h_s", z_hat)
-        h, w = hyper.h, hyper.w
-        bufs = self._param_buffers(hyper, n, h, w, dev)
-        y_hat = T.empty(n, h, w, M, dev)
-        bounds = ELIC_GROUPS + (M,)
-        for i in range(5):
-            c0, c1 = bounds[i], bounds[i + 1]
-            cg = c1 - c0
-            pa, pn = (bufs["a0"], bufs["n0"]) if i == 0 else (bufs["a"], bufs["n"])
-            if i > 0:
-                self._sub("channel_context_models", i - 1, y_hat.channels(0, c0), out=pn.channels(2 * M, 4 * M))
-                hip.axpby(pn.channels(2 * M, 4 * M), None, out=pa.channels(2 * M, 4 * M))
-            dec = hip.RansStreamDecoder(strings[0][i][0])
-            parts = []
-            for anchor in (True, False):
-                pin = pa if anchor else pn
-                if not anchor:
-                    self._ctx_conv(i)(parts[0], out=pin.channels(0, 2 * M))
-                gp = self._sub("entropy_parameters", i, pin)
-                idx = torch.empty((n, cg, h, w), dtype=torch.int32, device=dev)
-                hip.check(L.vc_gc_indexes(hip.stream(), gp.channels(0, cg).view(), table.data_ptr(), table.numel(), idx.data_ptr()),
-                          "vc_gc_indexes")
-                sq_idx = self._squeeze_np(idx.cpu().numpy(), anchor)
-                sym = dec.decode_stream(sq_idx.reshape(-1), *gc_tables).reshape(sq_idx.shape)
-                sym_full = torch.from_numpy(self._unsqueeze_np(sym, anchor)).to(dev)
-                full = T.empty(n, h, w, cg, dev)
-                hip.check(L.vc_gc_dequant(hip.stream(), sym_full.data_ptr(), gp.channels(cg, 2 * cg).view(), None, full.view()),
-                          "vc_gc_dequant")
-                parts.append(hip.quantize_mask(full, keep_parity=1 if anchor else 0, do_round=False))
-            hip.axpby(parts[0], parts[1], out=y_hat.channels(c0, c1))
+        device = coder != "host"
+        uploaded = isinstance(strings, hip.IransDecoder)
+        if device:
+            _check_coder(coder, waves)
+            hz, wz = int(shape[0]), int(shape[1])
+            if not (1 <= hz <= 4096 and 1 <= wz <= 4096):
+                raise hip.VcError(f"hyper-latent shape {hz}x{wz} is outside 1..4096")
+            if not uploaded and not (isinstance(strings, (list, tuple)) and strings and all(isinstance(b, (bytes, bytearray)) for b in strings)):
+                raise hip.VcError('ELIC.decompress(coder="device"): strings is one payload (bytes) per image, as compress(coder="device") '
+                                  "returns it -- this looks like the host-coded [[g0, ..., g4], z] lists")
+            dec = strings if uploaded else hip.IransDecoder(strings, waves, dev)
+            if dec.waves != int(waves):
+                raise hip.VcError(f"the uploaded payloads were read with waves {dec.waves}, not {waves}")
+            z_hat = T.empty(dec.images, hz, wz, self.N, dev)
+            dec.decode_eb(self.entropy_bottleneck.irans_tables(), self.entropy_bottleneck.device_params(), None, z_hat)
+            reader = (reader or DeviceFusedReader)(self, dec)
+        else:
+            if trace is not None:
+                raise hip.VcError('ELIC.decompress: trace= belongs to coder="device" (the host-coded path returns its latents in "y_hat")')
+            if uploaded or len(strings) != 2 or len(strings[0]) != 5 or \
+                    not all(isinstance(g, (list, tuple)) for g in list(strings[0]) + [strings[1]]):
+                raise hip.VcError('ELIC.decompress(coder="host"): strings is [[g0, ..., g4], z] with one byte string per image in each list '
+                                  '-- pass coder="device" for the payloads of compress(coder="device")')
+            t0 = time.process_time()
+            hz, wz = int(shape[0]), int(shape[1])
+            z_index = np.repeat(np.arange(self.N, dtype=np.int32), hz * wz)
+            z_sym = torch.from_numpy(np.stack([hip.rans_decode(b, z_index, *self.entropy_bottleneck.tables()) for b in strings[1]])).to(dev)
+            z_hat = T.empty(len(strings[1]), hz, wz, self.N, dev)     # (z_sym is bound to a local: it must outlive the launch that reads it)
+            hip.check(hip.lib().vc_eb_dequant(hip.stream(), z_sym.data_ptr(), self.entropy_bottleneck.device_params().data_ptr(),
+                                              None, z_hat.view()), "vc_eb_dequant")
+            reader = HostStreamReader(self, strings[0], self.STRINGS_PER_IMAGE)
+        y_hat = self._decode_passes(*self._hyper_buffers(z_hat), reader)
         x_hat = hip.nhwc_to_nchw(self.seq("g_s", y_hat))
-        torch.cuda.synchronize()
-        groups = [hip.nhwc_to_nchw(y_hat.channels(bounds[i], bounds[i + 1])) for i in range(5)]
-        return {"x_hat": x_hat, "cost_time": time.process_time() - t0, "y_hat": groups}
+        if not device:
+            torch.cuda.synchronize()
+            return {"x_hat": x_hat, "cost_time": time.process_time() - t0, "y_hat": self._nchw_groups(y_hat)}
+        if trace is not None:
+            self._trace_latents(trace, y_hat, z_hat)
+            trace["x_hat"] = x_hat
+        result = {"x_hat": x_hat, "y_hat": self._nchw_groups(y_hat)}
+        if not uploaded:                           # the one read, after everything is enqueued
+            dec.finish()
+        return result
 
     def forward(self, x):
         """NCHW CUDA tensor in; ``{"x_hat", "size"}`` out (``size`` = the -log2 likelihood sum the reference's
@@ -1125,7 +968,92 @@ def _flat_strings(codec_strings):
     return [b for g in groups for b in g] + list(z)
 
 
-class FlowGuidedB(nn.Module):
+class _BFrameBitstream(nn.Module):
+    """The real-bitstream surface the two B-frame models share (FlowGuidedB here, DeformB in icip2023.py): both code an offset
+    latent and a residual latent with two _Elic compressors, ``offset_compressor`` and ``residual_compressor``, an alignment step
+    between them and ``reconstructor`` behind them.  Each model keeps its features, its alignment and its frame-level checks."""
+
+    @staticmethod
+    def _coding_level(s):
+        """the quality level as the container stores it (fp32): both sides interpolate the gains from the same number"""
+        return float(np.float32(s))
+
+    def _coded_tail(self, F_, cond, off_temporal, align, res_lead, res_temporal, s, strings, shape, trace, coder, waves, reader):
+        """offset codec -> ``align(offset heads)`` = the three aligned maps -> residual codec -> reconstructor, on the compressors'
+        bitstream paths.  Encoder: ``F_`` the per-level buffers the offset encoder reads, ``res_lead`` per level the views the
+        residual encoder reads in front of the aligned map; decoder: both None, ``strings`` / ``shape`` instead.  ``cond``: the three
+        decoder-side views of the offset codec; ``*_temporal``: the two temporal conditioners.  Returns ``{"offset", "residual"}``
+        (encoder: the results of compress_t) and "x_hat" (NCHW)."""
+        enc = F_ is not None
+        t_off, t_res = ({}, {}) if trace is not None else (None, None)
+        oc, rc = self.offset_compressor, self.residual_compressor
+        off_cond = lambda dst: off_temporal.run(*cond, out=dst)  # noqa: E731
+        out = {}
+        if enc:
+            out["offset"] = oc.compress_t([F_[0]], [F_[1]], [F_[2]], *cond, off_cond, s, trace=t_off, coder=coder, waves=waves)
+            offs = out["offset"]["heads"]
+        else:
+            offs = oc.decompress_t(strings["offset"], shape, *cond, off_cond, s, trace=t_off, reader=reader)
+        comp = align(offs)
+        res_cond = lambda dst: res_temporal.run(*comp, out=dst)  # noqa: E731
+        if enc:
+            out["residual"] = rc.compress_t(*[list(lead) + [c] for lead, c in zip(res_lead, comp)], *comp, res_cond, s, res=tuple(comp),
+                                            trace=t_res, coder=coder, waves=waves)
+            xs = out["residual"]["heads"]
+        else:
+            xs = rc.decompress_t(strings["residual"], shape, *comp, res_cond, s, res=tuple(comp), trace=t_res, reader=reader)
+        if trace is not None:
+            trace.update({"offset": t_off, "residual": t_res})
+        out["x_hat"] = hip.nhwc_to_nchw(self.reconstructor.run(*xs))
+        return out
+
+    @staticmethod
+    def _compress_result(out, coder, waves):
+        """compress()'s result from the encoder's :meth:`_coded_tail`: "size" is the real bit count (8 x string bytes),
+        "size_estimate" -log2 p of the coded symbols on the device; the device coder adds "coder" and "waves"."""
+        strings = {k: out[k]["strings"] for k in ("offset", "residual")}
+        device = coder == "device"
+        nbytes = sum(len(b) for k in strings for b in (strings[k] if device else _flat_strings(strings[k])))
+        result = {"strings": strings, "shape": out["offset"]["shape"], "x_hat": out["x_hat"], "size": 8 * nbytes,
+                  "size_estimate": float((out["offset"]["bits"] + out["residual"]["bits"]).item())}
+        if device:
+            result.update({"coder": coder, "waves": int(waves)})
+        return result
+
+    def upload_payloads(self, strings, waves=4):
+        """The payloads of ``compress(coder="device")`` on their way to the device (pinned, non-blocking) and their sub-stream
+        headers read there: ``{"offset", "residual"}`` of hip.IransDecoder.  ``decompress`` takes the result in place of the
+        strings; the caller then owns the one look at the error words, ``finish()`` of both, after it has used x_hat."""
+        _check_coder("device", waves)
+        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"} or len(strings["offset"]) != len(strings["residual"]) \
+                or not all(isinstance(b, (bytes, bytearray)) for k in strings for b in strings[k]) or not strings["offset"]:
+            raise hip.VcError('strings: {"offset": [payload per image], "residual": [payload per image]}')
+        dev = self.offset_compressor.Gain.device
+        return {k: hip.IransDecoder(strings[k], waves, dev) for k in ("offset", "residual")}
+
+    def _decoder_inputs(self, strings, shape, coder, waves, xref1):
+        """decompress()'s strings checked against the references: (what the compressors' decompress_t take -- the host-coded lists
+        or uploaded decoders --, (hz, wz), the decoders whose error words this call has to read at its end)"""
+        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"}:
+            raise hip.VcError('strings: {"offset": ..., "residual": ...}')
+        hz, wz = int(shape[0]), int(shape[1])
+        mine = []
+        if coder == "device":
+            if not all(isinstance(v, hip.IransDecoder) for v in strings.values()):
+                strings = self.upload_payloads(strings, waves)
+                mine = list(strings.values())
+            images = strings["offset"].images
+            fits = all(d.images == xref1.shape[0] and d.waves == int(waves) for d in strings.values())
+        else:
+            images = len(strings["offset"][1]) if len(strings["offset"]) == 2 else None
+            fits = images == xref1.shape[0]
+        if (64 * hz, 64 * wz) != tuple(xref1.shape[2:]) or not fits:
+            raise hip.VcError(f"hyper-latent shape {hz}x{wz} / {images} image(s) / waves {waves} do not belong to references "
+                              f"{tuple(xref1.shape)} and the strings")
+        return strings, (hz, wz), mine
+
+
+class FlowGuidedB(_BFrameBitstream):
     def __init__(self):
         super().__init__()
         self.feature_extractor = MS_Feature()
@@ -1256,7 +1184,7 @@ class FlowGuidedB(nn.Module):
     SEARCH_RATIOS = (1, 2, 4, 8, 16)
 
     def _bitstream_pass(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio, strings=None, shape=None, trace=None, coder="host",
-                        waves=4):
+                        waves=4, reader=None):
         """The stages of :meth:`forward_device` with the two compressors on their bitstream paths; ``xcur`` is None on the decoder,
         which runs the reference-only stages through the same launches on the same buffer layouts (the per-level buffers keep
         their fcur slice, unused): every tensor the entropy path reads comes out of the same kernel instances on both sides."""
@@ -1283,43 +1211,21 @@ class FlowGuidedB(nn.Module):
             if l < 2:
                 flow = hip.avgpool_reflectpad(flow, 2, scale=0.5)
         cond = [F_[l].channels(0, 4 * chans[l]) for l in range(3)]
-        t_off, t_res = ({}, {}) if trace is not None else (None, None)
-        oc, rc = self.offset_compressor, self.residual_compressor
-        off_cond = lambda dst: self.offset_temporal_conditioner.run(cond[0], cond[1], cond[2], out=dst)  # noqa: E731
-        out = {}
-        if enc:
-            out["offset"] = oc.compress_t([F_[0]], [F_[1]], [F_[2]], cond[0], cond[1], cond[2], off_cond, s, trace=t_off, coder=coder,
-                                          waves=waves)
-            offs = out["offset"]["heads"]
-        else:
-            offs = oc.decompress_t(strings["offset"], shape, cond[0], cond[1], cond[2], off_cond, s, trace=t_off)
-        comp = []
-        for l, (off, div) in enumerate(((offs[0], self.offset_diversity_l1), (offs[1], self.offset_diversity_l2),
-                                        (offs[2], self.offset_diversity_l3))):
-            hc = off.c // 2
-            comp.append(div.run(fref1[l], off.channels(0, hc), flows[l][0], fref2[l], off.channels(hc, 2 * hc), flows[l][1]))
-        res_cond = lambda dst: self.residue_temporal_conditioner.run(comp[0], comp[1], comp[2], out=dst)  # noqa: E731
-        if enc:
-            out["residual"] = rc.compress_t([fcur[0], comp[0]], [fcur[1], comp[1]], [fcur[2], comp[2]], comp[0], comp[1], comp[2],
-                                            res_cond, s, res=tuple(comp), trace=t_res, coder=coder, waves=waves)
-            xs = out["residual"]["heads"]
-        else:
-            xs = rc.decompress_t(strings["residual"], shape, comp[0], comp[1], comp[2], res_cond, s, res=tuple(comp), trace=t_res)
-        if trace is not None:
-            trace.update({"offset": t_off, "residual": t_res})
-        out["x_hat"] = self.reconstructor.run(*xs)
-        return out
 
-    @staticmethod
-    def _coding_level(s):
-        """the quality level as the container stores it (fp32): both sides interpolate the gains from the same number"""
-        return float(np.float32(s))
+        def align(offs):
+            comp = []
+            for l, (off, div) in enumerate(zip(offs, (self.offset_diversity_l1, self.offset_diversity_l2, self.offset_diversity_l3))):
+                hc = off.c // 2
+                comp.append(div.run(fref1[l], off.channels(0, hc), flows[l][0], fref2[l], off.channels(hc, 2 * hc), flows[l][1]))
+            return comp
+        return self._coded_tail(F_ if enc else None, cond, self.offset_temporal_conditioner, align, [[f] for f in fcur] if enc else None,
+                                self.residue_temporal_conditioner, s, strings, shape, trace, coder, waves, reader)
 
-    CODERS = ("host", "device")
-
-    def _check_coder(self, coder, waves):
-        if coder not in self.CODERS or not hip.irans_waves_ok(waves):
-            raise hip.VcError(f"coder {coder!r} / waves {waves!r}: one of {self.CODERS}, waves a power of two in 1..16")
+    def _checked_down_ratio(self, down_ratio):
+        down_ratio = int(down_ratio)
+        if down_ratio not in self.SEARCH_RATIOS:
+            raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
+        return down_ratio
 
     def compress(self, xref1, xref2, scale1, scale2, xcur, s, down_ratio=None, trace=None, coder="host", waves=4):
         """Encode a B-frame for real.  NCHW CUDA tensors and host numbers as :meth:`forward`; ``down_ratio=None`` searches the
@@ -1334,7 +1240,7 @@ class FlowGuidedB(nn.Module):
         ``{"offset": [payload per image], "residual": [...]}``, the result gains "coder" and "waves" (the wave count the decoder needs),
         "size" is still 8 x the bytes of all payloads and x_hat is bit for bit that of the host-coded call."""
         _require_frames(xref1, xref2, xcur)
-        self._check_coder(coder, waves)
+        _check_coder(coder, waves)
         s = self._coding_level(s)
         r1, r2, c = hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), hip.nchw_to_nhwc(xcur)
         if down_ratio is None:                 # (the choice travels in the stream: the search itself needs no pinning)
@@ -1343,78 +1249,30 @@ class FlowGuidedB(nn.Module):
             if len(picks) != 1:
                 raise hip.VcError(f"the images of the batch choose different flow resolutions {picks}: encode them one by one")
             down_ratio = picks[0]
-        down_ratio = int(down_ratio)
-        if down_ratio not in self.SEARCH_RATIOS:
-            raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
+        down_ratio = self._checked_down_ratio(down_ratio)
         with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
             out = self._bitstream_pass(r1, r2, scale1, scale2, c, s, down_ratio, trace=trace, coder=coder, waves=waves)
-            x_hat = hip.nhwc_to_nchw(out["x_hat"])
-        strings = {k: out[k]["strings"] for k in ("offset", "residual")}
-        device = coder == "device"
-        nbytes = sum(len(b) for k in strings for b in (strings[k] if device else _flat_strings(strings[k])))
-        estimate = float((out["offset"]["bits"] + out["residual"]["bits"]).item())
-        result = {"strings": strings, "shape": out["offset"]["shape"], "down_ratio": down_ratio, "x_hat": x_hat, "size": 8 * nbytes,
-                  "size_estimate": estimate}
-        if device:
-            result.update({"coder": coder, "waves": int(waves)})
+        result = self._compress_result(out, coder, waves)
+        result["down_ratio"] = down_ratio
         return result
 
-    def upload_payloads(self, strings, waves=4):
-        """The payloads of ``compress(coder="device")`` on their way to the device (pinned, non-blocking) and their sub-stream
-        headers read there: ``{"offset", "residual"}`` of hip.IransDecoder.  :meth:`decompress` takes the result in place of the
-        strings; the caller then owns the one look at the error words, ``finish()`` of both, after it has used x_hat."""
-        self._check_coder("device", waves)
-        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"} or len(strings["offset"]) != len(strings["residual"]) \
-                or not all(isinstance(b, (bytes, bytearray)) for k in strings for b in strings[k]) or not strings["offset"]:
-            raise hip.VcError('strings: {"offset": [payload per image], "residual": [payload per image]}')
-        dev = self.offset_compressor.Gain.device
-        return {k: hip.IransDecoder(strings[k], waves, dev) for k in ("offset", "residual")}
-
-    def decompress(self, xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace=None, coder="host", waves=4):
+    def decompress(self, xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace=None, coder="host", waves=4, reader=None):
         """Decode the strings of :meth:`compress` from the two references alone: ``{"x_hat"}``.  ``coder="device"`` reads the
         payloads of ``compress(coder="device")`` (``waves`` as it returned it): one upload, then launches only -- no copy to the
         host and no synchronisation until x_hat is enqueued -- and one read of the decoders' error words at the end (VcError).
-        ``strings`` may be the result of :meth:`upload_payloads`; that last read is then the caller's."""
+        ``strings`` may be the result of :meth:`upload_payloads`; that last read is then the caller's.  ``reader``: the pass reader
+        of the payloads in place of the compressors' own (DeviceChainReader); tools/seq_codec_bench.py measures the other."""
         _require_frames(xref1, xref2)
-        self._check_coder(coder, waves)
-        if coder == "device":
-            return self._decompress_device(xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace, waves)
+        _check_coder(coder, waves)
         s = self._coding_level(s)
-        down_ratio = int(down_ratio)
-        if down_ratio not in self.SEARCH_RATIOS:
-            raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
-        if not isinstance(strings, dict) or set(strings) != {"offset", "residual"}:
-            raise hip.VcError('strings: {"offset": ..., "residual": ...}')
-        hz, wz = int(shape[0]), int(shape[1])
-        if (64 * hz, 64 * wz) != tuple(xref1.shape[2:]) or len(strings["offset"][1]) != xref1.shape[0]:
-            raise hip.VcError(f"hyper-latent shape {hz}x{wz} / {len(strings['offset'][1])} image(s) do not belong to references "
-                              f"{tuple(xref1.shape)}")
+        down_ratio = self._checked_down_ratio(down_ratio)
+        strings, shape, mine = self._decoder_inputs(strings, shape, coder, waves, xref1)
         with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
             out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), scale1, scale2, None, s, down_ratio,
-                                       strings=strings, shape=(hz, wz), trace=trace)
-            return {"x_hat": hip.nhwc_to_nchw(out["x_hat"])}
-
-    def _decompress_device(self, xref1, xref2, scale1, scale2, strings, shape, s, down_ratio, trace, waves):
-        s = self._coding_level(s)
-        down_ratio = int(down_ratio)
-        if down_ratio not in self.SEARCH_RATIOS:
-            raise hip.VcError(f"down_ratio {down_ratio} is not one of {self.SEARCH_RATIOS}")
-        uploaded = isinstance(strings, dict) and all(isinstance(v, hip.IransDecoder) for v in strings.values())
-        decoders = strings if uploaded else self.upload_payloads(strings, waves)
-        if set(decoders) != {"offset", "residual"}:
-            raise hip.VcError('strings: {"offset": ..., "residual": ...}')
-        hz, wz = int(shape[0]), int(shape[1])
-        if (64 * hz, 64 * wz) != tuple(xref1.shape[2:]) or any(d.images != xref1.shape[0] or d.waves != int(waves) for d in decoders.values()):
-            raise hip.VcError(f"hyper-latent shape {hz}x{wz} / {decoders['offset'].images} image(s) / waves {waves} do not belong to "
-                              f"references {tuple(xref1.shape)} and the uploaded payloads")
-        with hip.fp32_mode_pinned(hip.BITSTREAM_HS_MODE):
-            out = self._bitstream_pass(hip.nchw_to_nhwc(xref1), hip.nchw_to_nhwc(xref2), scale1, scale2, None, s, down_ratio,
-                                       strings=decoders, shape=(hz, wz), trace=trace)
-            x_hat = hip.nhwc_to_nchw(out["x_hat"])
-        if not uploaded:
-            for d in decoders.values():
-                d.finish()
-        return {"x_hat": x_hat}
+                                       strings=strings, shape=shape, trace=trace, reader=reader)
+        for d in mine:
+            d.finish()
+        return {"x_hat": out["x_hat"]}
 
     # -- motion-adaptive flow resolution (opt_helpers.py:23-51) --------------------------------------------
     def _predict_from_flow(self, flow, xref1, xref2, s1, s2):
@@ -1438,8 +1296,6 @@ class FlowGuidedB(nn.Module):
         s1, s2 = self.convert_scales(scale1, scale2)
         L, dev = hip.lib(), xcur.buf.device
         slots = L.vc_bits_slots()
-        partial = torch.empty(len(ratios) * slots, dtype=torch.float64, device=dev)
-        sse = torch.empty(len(ratios), dtype=torch.float64, device=dev)
         n, nr = xcur.n, len(ratios)
         partial = torch.empty(n * nr * slots, dtype=torch.float64, device=dev)
         sse = torch.empty(n * nr, dtype=torch.float64, device=dev)         # [image][ratio]
